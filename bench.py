@@ -20,7 +20,19 @@ Inputs are generated on the GPU and resident in HBM before timing; every
 step consumes a distinct batch of the stream.  Timing: W untimed warm-up
 steps, then K steps bracketed by barrier + synchronize; value = swipes of all
 ranks / the slowest rank's wall time.  The timed region carries no
-instrumentation.  Per-kernel times for the roofline come from a separate
+instrumentation.
+
+A plain run does only that: set-up, warm-up, the K timed steps, the outputs
+of the last step when `--dump-outputs DIR` asks for them, and the result
+line.  Everything below is measured or checked only with `--full`.
+
+`--dump-outputs DIR` writes what the timed path left after its last step as
+DIR/<name>.npy (dump_outputs): the BF.EXISTS answers of the last step and
+the HLL registers, in full when small and as a fixed seeded sample otherwise,
+with digests over the whole of both.  The generator is counter-based and
+seeded, so the same arguments give the same arrays from run to run.
+
+`--full`: per-kernel times for the roofline come from a separate
 REPLAY of the same steps: the register slab is zeroed, the W warm-up steps
 are re-run, and the K steps are replayed with a HIP event pair around every
 K1 kernel on the stream it runs on (ske_pass_times) -- the same batches from
@@ -31,9 +43,9 @@ sized for one MI355X) measured in the same process on its own context.
 
 N>1: one process per GPU (torch.distributed.run), RCCL ("nccl") process
 group; every rank runs its own stream over its own key shard with the Bloom
-replicated (no data-path collective; weak scaling).  After timing, every rank
-checks a verification stream through the SHIPPED classes: the stream names
-64 keys of a second universe (distributed.KeyMap), each rank runs K1 on the
+replicated (no data-path collective; weak scaling).  After timing, with
+`--full`, every rank checks a verification stream through the SHIPPED
+classes: the stream names 64 keys of a second universe (distributed.KeyMap), each rank runs K1 on the
 swipes of the keys it owns (or, with --exchange 1, routes its slice through
 distributed.SwipeExchange), and distributed.ShardedSketch answers union
 PFCOUNT, PFCOUNT of every key and a rollup by key name over RCCL; answers,
@@ -71,6 +83,11 @@ PASS_NAMES = ["k1", "k_part_a", "k_part_b", "k_part_c", "k_seg_d", "k_seg_e", "f
 K1_PASSES = 6  # PASS_NAMES[:6] are K1 kernels; the rest the stages of a host-fed call
 PMC_ROUNDS = ["r06", "r05", "r04", "r03", "r02"]  # newest committed PMC summaries first
 VERIFY_KEYS = 64
+# --dump-outputs: an array longer than DUMP_ELEMS is written as that many
+# draws of default_rng(DUMP_SEED); two sampled float32 arrays, their two
+# float64 index arrays and the float64 key sums are 32 MB at the most
+DUMP_ELEMS = 1 << 20
+DUMP_SEED = 20251003
 # swipes per GPU and step where it differs from the workload's own
 # step_swipes: C3 takes 2^28 since round 6 (its 1B-swipe stream in 4 steps;
 # 2^27 in round 5, 16 M before).  The segmented PFADD streams each key window
@@ -88,6 +105,14 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c3")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else: the instrumented "
+                         "replay and the roofline, stream_1b, rollup, host_fed, the oracle check, the CPU "
+                         "baseline and the secondary config (each still governed by its own option below); "
+                         "without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they left (the last step's answers, the HLL "
+                         "registers) as DIR/<name>.npy, sampled with a fixed seed where large")
     ap.add_argument("--secondary", default="auto",
                     help="config measured after the headline in the same process (N = 1 only); "
                          "auto = c2 when the headline is c3, none = skip")
@@ -826,7 +851,6 @@ class Run:
         self.nb = nb = max(1, min(args.max_batches, args.steps + args.warmup))
         self.batches = [engine.swipe_batch(p, (rank * nb + j) * n, n) for j in range(nb)]
         self.out = DeviceBuffer(engine.ctx, n)  # BF.EXISTS answers (the reference stores is_valid)
-        self.probes, self.nvalid = engine.swipes_stats(0, self.batches[0])
         self.width = synthetic.id_width(w)
         self.fixed = args.layout == "fixed"
         self.streams = [stream] + [torch.cuda.Stream() for _ in range(max(0, streams_n - 1))]
@@ -972,9 +996,85 @@ class Run:
         self.torch.as_tensor(_V(), device=self.dev).zero_()
         self.torch.cuda.synchronize()
 
+    def dump_outputs(self, path):
+        """--dump-outputs: what a caller of the timed path holds after its
+        last step, as path/<name>.npy (name + "_rank<r>" at N > 1):
+
+          answers          the BF.EXISTS answer (0 / 1) of every swipe of the
+                           last timed step, float32
+          registers        the HLL registers of this rank's keys after the
+                           warm-up and the timed steps (slot-major, 16384 per
+                           key), float32
+          answers_index, registers_index
+                           where an array above is a sample: the positions
+                           taken (float64; sorted draws of
+                           default_rng(DUMP_SEED), the same every run)
+          answers_valid    the number of 1 answers of the whole last step
+          registers_key_sums
+                           the sum of the 16384 registers of every key (of a
+                           seeded sample of DUMP_ELEMS keys beyond that many),
+                           so that a difference outside a sample shows too
+
+        An array of at most DUMP_ELEMS elements is written whole.  Where the
+        steps are not enqueued one after another on one stream (a persistent
+        launch, a graph, several streams), they share the answer buffer and
+        may overlap, so the last step's call is repeated alone first: same
+        batch, same filter, and registers it raised stay as they are."""
+        import numpy as np
+        torch, e, a, n = self.torch, self.engine, self.args, self.n
+        os.makedirs(path, exist_ok=True)
+        sfx = "_rank%d" % self.rank if self.world > 1 else ""
+        rng = np.random.default_rng(DUMP_SEED)
+
+        def save(name, arr, dtype=np.float32):
+            np.save(os.path.join(path, name + sfx + ".npy"), np.ascontiguousarray(arr, dtype=dtype))
+
+        def view(ptr, count):
+            class _V:
+                __cuda_array_interface__ = {"shape": (count,), "typestr": "|u1", "data": (ptr, False),
+                                            "version": 3, "strides": None}
+            return torch.as_tensor(_V(), device=self.dev)
+
+        def sampled(name, t):
+            if t.numel() <= DUMP_ELEMS:
+                save(name, t.cpu().numpy())
+                return
+            idx = np.sort(rng.integers(0, t.numel(), DUMP_ELEMS))
+            save(name, t[torch.from_numpy(idx).to(self.dev)].cpu().numpy())
+            save(name + "_index", idx, np.float64)
+
+        e.set_stream(self.stream.cuda_stream)
+        torch.cuda.synchronize()
+        if self.ex is None:
+            if self.persistent or self.graph is not None or len(self.streams) > 1:
+                last = self.batches[(a.warmup + a.steps - 1) % self.nb]
+                (e.swipes_fixed_async if self.fixed else e.swipes_async)(0, last, self.out)
+                torch.cuda.synchronize()
+                e.check_errors()
+            ans = view(self.out.ptr, n)
+            sampled("answers", ans)
+            save("answers_valid", [int(ans.sum(dtype=torch.int64))], np.float64)
+        # (--exchange: the answers return to the ranks that sent the swipes
+        # and are not kept; the registers are this rank's)
+        p, nb = C.c_void_p(), C.c_uint64()
+        e.ctx.call("ske_hll_slab", C.byref(p), C.byref(nb))
+        assert self.nslots * 16384 <= nb.value
+        if self.nslots:
+            regs = view(p.value, self.nslots * 16384)
+            sampled("registers", regs)
+            rows = regs.view(self.nslots, 16384)
+            keys = np.arange(self.nslots) if self.nslots <= DUMP_ELEMS else \
+                np.sort(rng.integers(0, self.nslots, DUMP_ELEMS))
+            keys = torch.from_numpy(keys).to(self.dev)
+            sums = torch.cat([rows[keys[i:i + 4096]].sum(1, dtype=torch.int64)
+                              for i in range(0, keys.numel(), 4096)])
+            save("registers_key_sums", sums.cpu().numpy(), np.float64)
+
     def roofline(self, pt, step_ms):
         """§3's roofline on the kernel that takes the most time."""
         a, n = self.args, self.n
+        # probes and valid swipes of batch 0 (a counting pass of its own)
+        self.probes, self.nvalid = self.engine.swipes_stats(0, self.batches[0])
         cus = self.torch.cuda.get_device_properties(self.dev).multi_processor_count
         seg = bool(pt) and len(pt) > 5 and pt[5][1] > 0
         # per launch of the per-sub-batch kernels: one sub-batch (bench batches
@@ -1220,7 +1320,10 @@ def main():
     shares.update({"rank_share_max": max(shares["swipes_per_step"]) / mean_n,
                    "rank_share_min": min(shares["swipes_per_step"]) / mean_n,
                    "slowest_rank": int(max(range(world), key=lambda r: shares["elapsed_s"][r]))})
-    pt = run.replay_instrumented() if args.pass_replay else None
+    if args.dump_outputs:
+        run.dump_outputs(args.dump_outputs)
+    full = args.full
+    pt = run.replay_instrumented() if full and args.pass_replay else None
     pt_rank = rank
     if world > 1 and pt is not None:
         # the per-pass times of the slowest rank (the one that bounds the
@@ -1250,24 +1353,30 @@ def main():
         "dtype": "u64",
         "data": "synthetic (device counter-based generator, seed %d)" % run.w.seed,
         "config": run.config(),
-        "roofline": {**run.roofline(pt, step_ms), "passes_of_rank": pt_rank},
+        "device_ms_per_step": step_ms,
         "preload_s": run.preload_s,
         "host_enqueue_us_per_step": host_enqueue * 1e6 / args.steps,
         "rank_shares": shares,
+        "full": full,
     }
     line["config"]["swipes_per_step_all_ranks"] = total_swipes
-    if args.stream_1b and not run.lds_k1 and not run.persistent and run.graph is None and not args.shard:
+    if args.dump_outputs:
+        line["outputs"] = args.dump_outputs
+    if full:
+        line["roofline"] = {**run.roofline(pt, step_ms), "passes_of_rank": pt_rank}
+    if full and args.stream_1b and not run.lds_k1 and not run.persistent and run.graph is None and not args.shard:
         line["stream_1b"] = checked(stream_1b, run, total_swipes, pt)
     if run.ex is not None:
         # cap_rows_per_peer / slack_used: what the timed steps were enqueued
         # with; slack_next: what settle() adapted it to for later batches
         line["exchange"] = {**run.ex.stats, "slack_next": run.ex.slack, "pipelined": run.ex.overlap}
-    if (args.rollup if args.rollup >= 0 else args.config == "c5") and not args.shard and run.w_all.zipf_lectures:
+    if full and (args.rollup if args.rollup >= 0 else args.config == "c5") and not args.shard \
+            and run.w_all.zipf_lectures:
         line["rollup"] = checked(rollup_bench, run, dist)
-    if world == 1 and args.host_fed and not run.lds_k1:
+    if full and world == 1 and args.host_fed and not run.lds_k1:
         line["host_fed"] = checked(host_fed, run.engine, run.batches[0])
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu and args.cpu_seconds > 0
-    if not args.no_check or want_cpu:
+    want_cpu = full and rank == 0 and world == 1 and not args.no_cpu and args.cpu_seconds > 0
+    if full and not args.no_check or want_cpu:
         orc = ge.load_oracle()
         chain = oracle_chain(run.engine, orc, run.w, run.p)
         if not args.no_check:
@@ -1287,7 +1396,7 @@ def main():
     sec = args.secondary
     if sec == "auto":
         sec = "c2" if args.config == "c3" else "none"
-    if world == 1 and sec != "none" and sec != args.config:
+    if full and world == 1 and sec != "none" and sec != args.config:
         line["secondary"] = secondary(args, sec, local, dev, dist)
     if rank == 0:
         print(json.dumps(line), flush=True)

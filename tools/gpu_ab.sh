@@ -11,7 +11,7 @@
 #   LIBS="new= base=tools/ab/libsketch_base.so"   name=SKE_LIB pairs ("" = in-tree build)
 #   REPS=2                        alternations
 #   MATRIX="--shard 8;"           ';'-separated extra bench argument sets ("" = the default step)
-#   BENCH="--no-cpu --secondary none --host-fed 0"   common bench arguments
+#   BENCH="--full --no-cpu --secondary none --host-fed 0"   common bench arguments (--full: the per-pass replay)
 #   PROF=1                        rocprofv3 --kernel-trace --stats of the first LIBS entry, first MATRIX set
 #   PMC="name=counters;..."       rocprofv3 --pmc passes of the first LIBS entry (one run per pass)
 set -o pipefail
@@ -20,7 +20,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 TAG=${TAG:-ab}
 REPS=${REPS:-2}
-BENCH=${BENCH:---no-cpu --secondary none --host-fed 0}
+BENCH=${BENCH:---full --no-cpu --secondary none --host-fed 0}
 nproc > $O/${TAG}_host.txt
 if [ -n "$TESTS" ]; then
   T=$TESTS; [ "$T" = all ] && T=tests

@@ -5,6 +5,8 @@
 # phase timeline.  Every GPU step has its own time limit; the first failure
 # ends the session.
 mkdir -p gpurun_out
+B=${BENCH_OUT:-bench_out}  # the bench lines' logs
+mkdir -p $B
 export TMPDIR=/tmp
 nproc > gpurun_out/host.txt; lscpu | grep -E "Model name|^CPU\(s\)" >> gpurun_out/host.txt
 if [ -z "$SKIP_TESTS" ]; then
@@ -16,8 +18,8 @@ if [ -z "$SKIP_TESTS" ]; then
   if [ $rc -ne 0 ]; then exit $rc; fi
 fi
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 300 python bench.py > gpurun_out/bench.log 2>&1; rc=$?
-  echo "bench rc=$rc"; tail -1 gpurun_out/bench.log
+  timeout -k 10 300 python bench.py --full > $B/bench.log 2>&1; rc=$?
+  echo "bench rc=$rc"; tail -1 $B/bench.log
   if [ $rc -ne 0 ]; then exit $rc; fi
 fi
 if [ -n "$PROF" ]; then
@@ -27,9 +29,9 @@ if [ -n "$PROF" ]; then
 fi
 IFS=';' read -ra SETS <<< "$MATRIX"
 for v in "${SETS[@]}"; do
-  timeout -k 10 300 python bench.py --no-cpu --secondary none $v > gpurun_out/bench_m.log 2>&1; rc=$?
-  if [ $rc -ne 0 ]; then echo "bench [$v] rc=$rc"; tail -5 gpurun_out/bench_m.log; exit $rc; fi
-  echo -n "[$v] "; python -c "import json; d=json.loads(open('gpurun_out/bench_m.log').read().strip().splitlines()[-1]); r=d['roofline']; print('%.3e swipes/s  step %.4f ms  kernel %s %.4f ms  enq %.1f us  %s frac=%.2f  passes %s' % (d['value'], d['ms_per_step'], r['kernel'], r['kernel_ms'], d['host_enqueue_us_per_step'], d['config']['k1_variant'], r['frac'], {k: round(v['ms'], 4) for k, v in r['passes'].items()}))"
+  timeout -k 10 300 python bench.py --full --no-cpu --secondary none $v > $B/bench_m.log 2>&1; rc=$?
+  if [ $rc -ne 0 ]; then echo "bench [$v] rc=$rc"; tail -5 $B/bench_m.log; exit $rc; fi
+  echo -n "[$v] "; python -c "import json; d=json.loads(open('$B/bench_m.log').read().strip().splitlines()[-1]); r=d['roofline']; print('%.3e swipes/s  step %.4f ms  kernel %s %.4f ms  enq %.1f us  %s frac=%.2f  passes %s' % (d['value'], d['ms_per_step'], r['kernel'], r['kernel_ms'], d['host_enqueue_us_per_step'], d['config']['k1_variant'], r['frac'], {k: round(v['ms'], 4) for k, v in r['passes'].items()}))"
 done
 if [ -n "$STAMPS" ]; then
   for t in ${STAMP_TILES:-2}; do
