@@ -47,7 +47,9 @@
 // 16-copy counter table, pass A at three blocks per CU, the register
 // pre-check in pass A, PFADD by owned register lines, pass C on a side or
 // CU-masked stream; in round 4 also pair runs padded to 128-B lines, the
-// tile parity unrolled, and a two-phase pass C.
+// tile parity unrolled, and a two-phase pass C.  Round 7 keeps one slower
+// form selectable at build time, for A/B only: pass A's sort as count, scan,
+// place, which fits three blocks per CU (SKE_PA_PLACE, SKE_PA_BPC).
 //
 // Placement of blocks on XCDs is a speed matter only; every (tile, slice) run
 // is read by exactly one block, and fail marks are only ever set.
@@ -211,8 +213,10 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t part_rsrc(const void *p, uint3
 // pass A3's id prefetch distance: 1 -- a tile's ids load after the previous
 // tile's atomics (from offsets loaded at that tile's start); 2 -- at the
 // previous tile's start, from offsets loaded a tile earlier
+// 0 (default): 2 where it fits the instantiation's registers, else 1 (1536-swipe
+// tiles and the three-blocks-per-CU form, 80 VGPRs: 2 would spill)
 #ifndef SKE_PA_AHEAD
-#define SKE_PA_AHEAD (kTileFl == 1024 ? 2 : 1)  // (1536-swipe tiles: 2 would spill)
+#define SKE_PA_AHEAD 0
 #endif
 typedef uint32_t part_u32x4 __attribute__((ext_vector_type(4)));
 template <int BIT, class T> __device__ __forceinline__ T nt_ld(const T *p) {
@@ -420,11 +424,34 @@ __global__ void __launch_bounds__(kPaBlock, KM <= 11 ? 8 : 4) k_part_a(const Par
 // ms, round 2):
 //   * records are (bit offset in the slice PAIR: 20 bits) | swipe << 20,
 //     one v_and_or per probe (pass B of the pair reads the offset as is);
-//   * a counter counts in 4s from a bias of (its LDS word index) << 18, so an
-//     atomic's return value >> 16 is its own byte offset in the counter
-//     array; after the scan the counter holds 4 * start - bias, so a
+//   * the sort places by the counting atomic's rank (SKE_PA_PLACE 0, the
+//     default): a counter counts in 4s from a bias of (its LDS word index)
+//     << 18, so an atomic's return value >> 16 is its own byte offset in the
+//     counter array; after the scan the counter holds 4 * start - bias, so a
 //     record's byte offset in the tile's LDS record array is the atomic's
-//     return value plus that word: one shift and one add per record;
+//     return value plus that word: one shift and one add per record.  The
+//     record and the rank of every probe (44 VGPRs) stay live across three
+//     barriers;
+//   * count, scan, place (SKE_PA_PLACE 1, round 7, not the default): the
+//     probe walk keeps each probe's x (22 VGPRs) and counts it with a
+//     non-returning LDS add of 1; the scan leaves every counter at 4 * (its
+//     slice's start); placement is one returning add of 4 per kept x -- the
+//     record's byte offset -- and the store of (x & 0xfffff) | swipe << 20
+//     there.  A lane past the batch keeps the sink's x (sink << kPSliceLog),
+//     so placement has no select.  It fits three blocks per CU (SKE_PA_BPC
+//     3: 79 VGPRs, no spills, ids one tile ahead) where the rank form spills,
+//     and is slower all the same: per 2^25 sub-batch 0.426 ms (rank form, two
+//     blocks) -> 0.470 (two blocks) / 0.441 (three); the same LDS cycles and
+//     fewer VALU instructions, but (it seems) the placement's returning adds
+//     have no VALU work of their wave to hide behind, which the count's had
+//     (profiles/r07_ab_pa_place.txt);
+//   * from barrier 1 to the end of the copy-out a wave runs at priority 1
+//     (SKE_PA_PRIO, round 7): the scan between barriers 1 and 3 is a few
+//     dozen instructions per wave on which the block's other seven waves
+//     wait, and at equal priority they queued behind the other block's
+//     hashing.  0.428 -> 0.396 ms per sub-batch, 8.64-8.67 -> 8.38-8.47 ms
+//     per 2^28 step; raised from barrier 3 on only, or to priority 3, it
+//     changes nothing more;
 //   * full tiles take a probe loop without the past-the-batch select;
 //   * the two slices of a pair are counted apart but their runs are
 //     adjacent with no gap (dense pair runs, round 4): pass B reads one word
@@ -441,13 +468,59 @@ constexpr uint32_t kOORa = 0x80000000u;  // a buffer offset past every range: lo
 #ifndef SKE_PA_WAIT_LAST
 #define SKE_PA_WAIT_LAST 1  // round 4 A/B: pass A 0.226-0.230 -> 0.225 ms
 #endif
+// the order of the sort, the blocks per CU and the sort phases' wave
+// priority: build-time A/B knobs
+#ifndef SKE_PA_PLACE
+#define SKE_PA_PLACE 0
+#endif
+// Blocks per CU of the instantiation whose LDS allows three (1024 counters,
+// 1024-swipe tiles, no group layout: 53 296 B per block); the others run two.
+// Three blocks are 6 waves per SIMD, an allocation of at most 80 VGPRs.
+#ifndef SKE_PA_BPC
+#define SKE_PA_BPC 2
+#endif
+static_assert(SKE_PA_BPC == 2 || SKE_PA_BPC == 3, "pass A at two or three blocks per CU");
+#ifndef SKE_PA_PRIO
+#define SKE_PA_PRIO 1
+#endif
+static_assert(SKE_PA_PRIO >= 0 && SKE_PA_PRIO <= 3, "s_setprio takes 0..3");
+// a count nobody reads back: an LDS add without a return value
+__device__ __forceinline__ void pa_count(uint32_t *p) {
+    __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+constexpr uint32_t part_a3_lds(uint32_t kCnt, bool GL, uint32_t TILE) {  // sizeof(k_part_a3's Lds)
+    const uint32_t rec = TILE * 11 + (GL ? 4 * (kCnt / 2) : 0);
+    return (4 * (2 * kCnt + rec + (GL ? rec / 4 : 1) + 512 / 64 + 1) + 15) & ~15u;
+}
+constexpr uint32_t part_a3_bpc(uint32_t kCnt, bool GL, uint32_t TILE) {
+    return SKE_PA_BPC == 3 && 3 * part_a3_lds(kCnt, GL, TILE) <= 160 * 1024 ? 3 : 2;
+}
+// The tile's four barriers (both orders of the sort) and what each protects:
+//   1  after the count: every probe of the tile is counted before the scan
+//      reads the counters; a wave passes it only after its own copy-out
+//      reads of the previous tile's srec have returned (lgkmcnt(0)), so with
+//      barriers 2 and 3 behind it too no placement overwrites a record that a
+//      copy-out has yet to read;
+//   2  after the wave sums: swsum is complete before the block prefix, and
+//      every thread has read its counts before barrier 3's writers;
+//   3  after the scanned starts are written: placement adds only to scanned
+//      counters (SKE_PA_PLACE 0: reads them), and swsum / stot / dmap are read
+//      before the next tile rewrites them (its barriers 1 and 2 come first);
+//   4  after the placement: srec is complete before the copy-out reads it.
+//      The other parity's counters are cleared between 3 and 4 -- their last
+//      users, the placement adds of the tile before, ended before that
+//      tile's barrier 4 -- so the next tile counts on clear counters right
+//      after barrier 4 while this parity's scanned values are left alone
+//      until the tile after next's clearing.
 // GL: the group layout (PartArgs::gcap).  A block takes whole groups of 8
 // consecutive tiles, one tile after the other, and keeps each of its units'
 // place in the group's region in a register; every run starts on a 16-B
 // piece (padded to 4 records in LDS and in the region), so the copy-out stays
 // one 16-B store per piece, to the place an LDS map gives the piece's unit.
 template <int KM, uint32_t kCnt, bool GL = false, uint32_t TILE = 1024>
-__global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two blocks per CU
+__global__ void __launch_bounds__(512, 2 * part_a3_bpc(kCnt, GL, TILE)) k_part_a3(const PartArgs A) {
+    static_assert(KM == 11, "part_a3_lds");
+    constexpr int kAhead = SKE_PA_AHEAD ? SKE_PA_AHEAD : (TILE == 1024 && part_a3_bpc(kCnt, GL, TILE) == 2 ? 2 : 1);
     constexpr uint32_t kT = 512;
     constexpr uint32_t kU = TILE / kT, kTile = TILE;
     constexpr uint32_t kPer = kCnt / kT;  // counters per thread: kPer / 2 whole pairs
@@ -455,13 +528,16 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
     constexpr uint32_t kRecWords = kTile * KM + (GL ? 4 * (kCnt / 2) : 0);
     constexpr uint32_t kCo = (kRecWords / 4 + kT - 1) / kT;  // 16-B copy-out pieces per thread
     constexpr uint32_t kMap = GL ? kRecWords / 4 : 1;        // GL: a piece's place - its LDS place
-    // counter bias: counter c starts at c << kSB, so an atomic's return value
-    // >> kRS (= kSB - 2) is its byte offset 4 c as long as 4 * rank stays below
-    // bit kRS (1024-swipe tiles: 18 / 16; 1536: 19 / 17)
+    // SKE_PA_PLACE 0, the counter bias: counter c starts at c << kSB, so an
+    // atomic's return value >> kRS (= kSB - 2) is its byte offset 4 c as long
+    // as 4 * rank stays below bit kRS (1024-swipe tiles: 18 / 16; 1536: 19 / 17)
     constexpr uint32_t kSB = 4u * kRecWords < 65536u ? 18 : 19, kRS = kSB - 2;
-    static_assert(kCnt % (2 * kT) == 0 && 4u * kRecWords < (1u << kRS) && kRecWords < 65536u &&
-                      (2 * kCnt - 1) < (1u << (32 - kSB)) && kTile % kT == 0 && kTile <= 2048,
-                  "whole pairs per thread; a rank * 4 below bit kRS; starts fit 16 bits; 11-bit swipe field");
+    static_assert(kCnt % (2 * kT) == 0 && kRecWords < 65536u && kTile % kT == 0 && kTile <= 2048,
+                  "whole pairs per thread; starts fit 16 bits; 11-bit swipe field");
+    static_assert(SKE_PA_PLACE || (4u * kRecWords < (1u << kRS) && (2 * kCnt - 1) < (1u << (32 - kSB))),
+                  "a rank * 4 below bit kRS; the bias of the last counter fits");
+    // a counter's cleared value
+    auto czero = [](uint32_t c) { return SKE_PA_PLACE ? 0u : c << kSB; };
     // one LDS object, counters first: it sits at LDS address 0, so a probe's
     // counter address is its slice field shifted and added to the parity's
     // base (v_bfe + v_lshl_add: two VALU per probe)
@@ -473,13 +549,15 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
         uint32_t stot;
     };
     __shared__ Lds lds;
+    static_assert(sizeof(Lds) == part_a3_lds(kCnt, GL, TILE), "the blocks per CU are worked out from this size");
     uint32_t *const cnt = lds.cnt, *const srec = lds.srec, *const swsum = lds.swsum;
     uint32_t &stot = lds.stot;
     static_assert((kCnt & (kCnt - 1)) == 0, "parity base above the counter index bits");
+    static_assert(kPSliceLog + __builtin_ctz(kCnt) <= 32, "the sink's x (sink << kPSliceLog) keeps its slice field");
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t nunits = A.nunits;
     const uint32_t sink = 2 * nunits;  // the sink pair's first slice
-    for (uint32_t c = tid; c < 2 * kCnt; c += kT) cnt[c] = c << kSB;
+    for (uint32_t c = tid; c < 2 * kCnt; c += kT) cnt[c] = czero(c);
     lds_barrier();
     // Every global load and store below is issued by every wave the same
     // number of times (buffer operations; a lane or a whole call with nothing
@@ -523,13 +601,13 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
             offsets(t < gt1 ? t : gt0, u, nb_[u], ne_[u]);
             part_id_load(rbytes, nb_[u], ne_[u], it[u]);
         }
-        if (SKE_PA_AHEAD == 2) {
+        if (kAhead == 2) {
             const uint32_t t1 = t < gt1 && tnext(t) < gt1 ? tnext(t) : (t < gt1 ? t : gt0);
 #pragma unroll
             for (uint32_t u = 0; u < kU; u++) offsets(t1, u, nb_[u], ne_[u]);
         }
     }
-    const uint8_t *cntb = reinterpret_cast<const uint8_t *>(cnt);
+    [[maybe_unused]] const uint8_t *cntb = reinterpret_cast<const uint8_t *>(cnt);
     uint8_t *srecb = reinterpret_cast<uint8_t *>(srec);
     uint8_t *const cntw = reinterpret_cast<uint8_t *>(cnt);
     // a probe's slice (kCnt - 1 masks it: slices < kCnt), as one v_bfe the
@@ -543,10 +621,12 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
     auto tile = [&](const uint32_t t, const uint32_t par) {
         const uint32_t cb = par * kCnt;
         const uint32_t pb = cb * 4;  // the parity's byte base, above (kCnt - 1) * 4
-        uint32_t rv[kU][KM], rp[kU][KM];
+        // SKE_PA_PLACE 1: rv holds the probes' x; 0: their records, rp their ranks
+        uint32_t rv[kU][KM];
+        [[maybe_unused]] uint32_t rp[kU][KM];
         const uint32_t tn = tnext(t) < gt1 ? tnext(t) : t;
         PartId itn[kU];
-        if (SKE_PA_AHEAD == 2) {
+        if (kAhead == 2) {
             // the next tile's ids (nb_ / ne_ hold its offsets), then the
             // offsets of the tile after it
             const uint32_t tn2 = tnext(tn) < gt1 ? tnext(tn) : tn;
@@ -575,32 +655,55 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
             const uint32_t lu20 = lu << 20;
             ProbeWalk32 wk;
             wk.init(ha, hb, part_div(L));
-            if (full) {
+            if constexpr (SKE_PA_PLACE) {
+                // count: non-returning adds, nothing to wait for before barrier 1
+                if (full) {
 #pragma unroll
-                for (int q = 0; q < KM; q++) {
-                    const uint32_t x = wk.x;
-                    rv[u][q] = (x & 0xfffffu) | lu20;
-                    rp[u][q] = atomicAdd(reinterpret_cast<uint32_t *>(cntw + part_slice(x) * 4 + pb), 4u);
-                    if (q + 1 < KM) wk.step(L.d);
+                    for (int q = 0; q < KM; q++) {
+                        const uint32_t x = wk.x;
+                        rv[u][q] = x;
+                        pa_count(reinterpret_cast<uint32_t *>(cntw + part_slice(x) * 4 + pb));
+                        if (q + 1 < KM) wk.step(L.d);
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < KM; q++) {
+                        const uint32_t x = act ? wk.x : sink << kPSliceLog;
+                        rv[u][q] = x;
+                        pa_count(reinterpret_cast<uint32_t *>(cntw + part_slice(x) * 4 + pb));
+                        if (q + 1 < KM) wk.step(L.d);
+                    }
                 }
             } else {
+                if (full) {
 #pragma unroll
-                for (int q = 0; q < KM; q++) {
-                    const uint32_t x = wk.x;
-                    rv[u][q] = (x & 0xfffffu) | lu20;
-                    rp[u][q] = atomicAdd(reinterpret_cast<uint32_t *>(cntw + (act ? part_slice(x) : sink) * 4 + pb), 4u);
-                    if (q + 1 < KM) wk.step(L.d);
+                    for (int q = 0; q < KM; q++) {
+                        const uint32_t x = wk.x;
+                        rv[u][q] = (x & 0xfffffu) | lu20;
+                        rp[u][q] = atomicAdd(reinterpret_cast<uint32_t *>(cntw + part_slice(x) * 4 + pb), 4u);
+                        if (q + 1 < KM) wk.step(L.d);
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < KM; q++) {
+                        const uint32_t x = wk.x;
+                        rv[u][q] = (x & 0xfffffu) | lu20;
+                        rp[u][q] =
+                            atomicAdd(reinterpret_cast<uint32_t *>(cntw + (act ? part_slice(x) : sink) * 4 + pb), 4u);
+                        if (q + 1 < KM) wk.step(L.d);
+                    }
                 }
+                // lgkmcnt(0): this swipe's atomics, once (SKE_PA_WAIT_LAST: only
+                // after the last swipe, so the first one's atomics overlap the
+                // second one's hash)
+                if (!SKE_PA_WAIT_LAST || u + 1 == kU) __builtin_amdgcn_s_waitcnt(0xc07f);
             }
-            // lgkmcnt(0): this swipe's atomics, once (SKE_PA_WAIT_LAST: only
-            // after the last swipe, so the first one's atomics overlap the
-            // second one's hash)
-            if (!SKE_PA_WAIT_LAST || u + 1 == kU) __builtin_amdgcn_s_waitcnt(0xc07f);
         }
-        lds_barrier();
+        lds_barrier();  // 1
+        if (SKE_PA_PRIO) __builtin_amdgcn_s_setprio(SKE_PA_PRIO);
 #pragma unroll
         for (uint32_t u = 0; u < kU; u++) {  // the next tile's ids
-            if (SKE_PA_AHEAD == 2) it[u] = itn[u];
+            if (kAhead == 2) it[u] = itn[u];
             else part_id_load(rbytes, nb_[u], ne_[u], it[u]);
         }
         // exclusive scan over pairs of their two slices' counts
@@ -608,13 +711,13 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
 #pragma unroll
         for (uint32_t j = 0; j < kPer; j++) {
             const uint32_t c = cb + tid * kPer + j;
-            v[j] = (cnt[c] - (c << kSB)) >> 2;
+            v[j] = SKE_PA_PLACE ? cnt[c] : (cnt[c] - (c << kSB)) >> 2;
         }
 #pragma unroll
         for (uint32_t j = 0; j < kPer; j += 2) s += GL ? (v[j] + v[j + 1] + 3) & ~3u : v[j] + v[j + 1];
         const uint32_t incl = part_wave_scan(s);
         if (lane == 63) swsum[wave] = incl;
-        lds_barrier();
+        lds_barrier();  // 2
         uint32_t run = incl - s;
         for (uint32_t w = 0; w < wave; w++) run += swsum[w];
 #pragma unroll
@@ -635,22 +738,40 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
             }
             __builtin_amdgcn_raw_buffer_store_b32(W, roff, un < nunits ? (un * A.off_stride + t) * 4 : kOORa, 0, 0);
             if (g == sink) stot = run;
-            cnt[c] = 4 * run - (c << kSB);
-            cnt[c + 1] = 4 * (run + v[j]) - ((c + 1) << kSB);
+            // (the slice's start in bytes: where its first record goes)
+            cnt[c] = 4 * run - czero(c);
+            cnt[c + 1] = 4 * (run + v[j]) - czero(c + 1);
             run += GL ? (n2 + 3) & ~3u : n2;
         }
-        lds_barrier();
+        lds_barrier();  // 3
 #pragma unroll
-        for (uint32_t u = 0; u < kU; u++)
+        for (uint32_t u = 0; u < kU; u++) {
+            if constexpr (SKE_PA_PLACE) {
+                // place: the add's return value is the record's byte offset.  A
+                // swipe's KM adds are issued before its first store (the stores
+                // could alias the counters for all the compiler knows, so adds
+                // and stores in turn would be KM LDS round trips one after
+                // the other); the hashing state is dead here, so the KM
+                // offsets cost no register at the kernel's peak.
+                uint32_t at[KM];
 #pragma unroll
-            for (int q = 0; q < KM; q++) {
-                const uint32_t r = rp[u][q];
-                *reinterpret_cast<uint32_t *>(srecb + (r + *reinterpret_cast<const uint32_t *>(cntb + (r >> kRS)))) =
-                    rv[u][q];
+                for (int q = 0; q < KM; q++)
+                    at[q] = atomicAdd(reinterpret_cast<uint32_t *>(cntw + part_slice(rv[u][q]) * 4 + pb), 4u);
+#pragma unroll
+                for (int q = 0; q < KM; q++)
+                    *reinterpret_cast<uint32_t *>(srecb + at[q]) = (rv[u][q] & 0xfffffu) | ((u * kT + tid) << 20);
+            } else {
+#pragma unroll
+                for (int q = 0; q < KM; q++) {
+                    const uint32_t r = rp[u][q];
+                    *reinterpret_cast<uint32_t *>(srecb + (r + *reinterpret_cast<const uint32_t *>(cntb + (r >> kRS)))) =
+                        rv[u][q];
+                }
             }
+        }
         const uint32_t nb = (cb ^ kCnt);
-        for (uint32_t g = tid; g <= sink + 1; g += kT) cnt[nb + g] = (nb + g) << kSB;
-        lds_barrier();
+        for (uint32_t g = tid; g <= sink + 1; g += kT) cnt[nb + g] = czero(nb + g);
+        lds_barrier();  // 4
         const uint32_t total = stot;
         // a fixed number of 16-B pieces per thread (those past the tile's
         // total go out of range)
@@ -681,6 +802,7 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned int, src[jr]),
                                                    rdst, j * 4 < total ? at : kOORa, 0, nt_aux<4>());
         }
+        if (SKE_PA_PRIO) __builtin_amdgcn_s_setprio(0);
     };
     uint32_t par = 0;
     for (uint32_t t = tfirst; t < gt1; t = tnext(t), par ^= 1) tile(t, par);
@@ -1413,6 +1535,8 @@ __device__ __forceinline__ uint32_t seg_last_le(const uint32_t *a, uint32_t n, u
 // publishes without waiting on anything).  A wait that never ends sets error
 // bit 4 (reported as the call's error) after ~1 s.
 static_assert(kSegChunk == 8192, "the arena's chunk arithmetic");
+static_assert(!SKE_SEG_ARENA || kSegRunSw <= kSegChunk,
+              "the arena: a run's records of one bucket span at most two chunks (1536-swipe tiles: SKE_SEG_ARENA 0)");
 // fill counts 256 B apart: every run adds to every bucket's, and counters
 // packed in a few lines would queue on the few memory channels holding them
 #ifndef SKE_SEG_FILL_STRIDE
@@ -1648,15 +1772,7 @@ __global__ void __launch_bounds__(T, SegC1<T>::WPE) k_seg_c1(const PartArgs A, c
     }
 }
 
-// C1 with the next run's streams in flight (chains whose fail lists of a run
-// fit NP 16-B pieces per thread: C3/C5's 152 slice pairs take 1216 of 2048).
-// The run's slots, HLL words and fail lists are loaded into registers while
-// the previous run is sorted and copied out; every memory operation after
-// those loads is a buffer operation issued a fixed number of times (offsets
-// past a range for lanes with nothing to do), so the wait for them is exact
-// and does not wait for the copy-out's stores.  Same output as k_seg_c1.
 __global__ void __launch_bounds__(1024) k_seg_scan(const SegArgs S) {
-
     __shared__ uint32_t ws[16];
     const uint32_t h = blockIdx.x, tid = threadIdx.x;
     const uint32_t *oa = S.o1 + size_t(h) * kSegMaxRuns, *ob = oa + kSegMaxRuns;
@@ -2633,7 +2749,8 @@ hipError_t launch_swipes_part(const ChainDev &ch, const PartBatch *bt, uint32_t 
     const bool flist = part_flist(A) && A.flist != nullptr;
     const bool pairs = A.nlinks == 1;  // a one-link chain is probed in slice pairs (128 KiB images)
     const unsigned ga = unsigned(cus) * (km <= 11 ? 2u : 1u) / kPGroups * kPGroups;  // blocks past a group's tiles exit
-    const unsigned g2 = unsigned(cus) * 2 / kPGroups * kPGroups;  // k_part_a3: two blocks per CU
+    // k_part_a3: the resident set, two or three blocks per CU (part_a3_bpc)
+    auto ga3 = [&](uint32_t bpc) { return unsigned(cus) * bpc / kPGroups * kPGroups; };
     const unsigned gb = unsigned(cus) * (pairs ? 1 : 2) / kPGroups * kPGroups;  // all resident
     for (uint32_t j = 0; j < nb; j++) {
         const PartBatch &B = bt[j];
@@ -2700,11 +2817,14 @@ hipError_t launch_swipes_part(const ChainDev &ch, const PartBatch *bt, uint32_t 
             A.out = B.out ? B.out + s0 : nullptr;
             if (hook) hook(hook_user, 0, 0, st);
             if (A.gcap)  // the group layout (C3/C5 by default)
-                hipLaunchKernelGGL((k_part_a3<11, 1024, true>), dim3(g2), dim3(512), 0, st, A);
+                hipLaunchKernelGGL((k_part_a3<11, 1024, true>), dim3(ga3(part_a3_bpc(1024, true, 1024))), dim3(512), 0, st,
+                                   A);
             else if (flist && A.nunits < 512)  // C3/C5: 152 pairs, two counters per thread
-                hipLaunchKernelGGL((k_part_a3<11, 1024, false, kTileFl>), dim3(g2), dim3(512), 0, st, A);
+                hipLaunchKernelGGL((k_part_a3<11, 1024, false, kTileFl>), dim3(ga3(part_a3_bpc(1024, false, kTileFl))),
+                                   dim3(512), 0, st, A);
             else if (flist)
-                hipLaunchKernelGGL((k_part_a3<11, 2048, false, kTileFl>), dim3(g2), dim3(512), 0, st, A);
+                hipLaunchKernelGGL((k_part_a3<11, 2048, false, kTileFl>), dim3(ga3(part_a3_bpc(2048, false, kTileFl))),
+                                   dim3(512), 0, st, A);
             else if (km <= 11)
                 hipLaunchKernelGGL(k_part_a<11>, dim3(ga), dim3(kPaBlock), 0, st, A);
             else
