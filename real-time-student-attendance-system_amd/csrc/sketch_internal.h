@@ -135,7 +135,8 @@ hipError_t launch_swipes_xr(const ChainDev &ch, const uint8_t *bytes, const uint
                             int cus, int region_u, int finish_u, hipStream_t st);
 
 // sketch_part.hip -- partitioned K1 (probe records routed to LDS-resident
-// 64 KiB slices of each link) for chains larger than the LDS image
+// 64 KiB slices of each link) for chains larger than the LDS image; its
+// segmented PFADD is sketch_seg.hip, what the two share sketch_part.h
 constexpr int kPSliceLog = 19;
 constexpr uint32_t kPSliceBits = 1u << kPSliceLog;
 constexpr uint32_t kPMaxSlices = 2047;

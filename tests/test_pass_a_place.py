@@ -1,6 +1,5 @@
 """Pass A of the fail-list path (k_part_a3, sketch_part.hip): the tile's
-counting sort in either order (by the counting atomic's rank, or count ->
-scan -> place: the build's SKE_PA_PLACE), at two or three blocks per CU.
+counting sort, placed by the counting atomic's rank, at two blocks per CU.
 
 Every case runs the partitioned K1 (variant 3) on a one-link k = 11 chain
 (RESERVE 0.001) and compares the answers and all registers bit-exactly with
@@ -12,9 +11,9 @@ The shapes are the smallest at which this sort can go wrong:
   parities);
 - 8 * 1024 + 1 swipes on a filter of 1e5 capacity (four slices: runs of
   thousands of records per tile), and 1600 tiles + 1 swipes on the same
-  filter: tiles are dealt to 8 groups and a group's to a third or a quarter
-  of the resident blocks (96 or 64), so 200 tiles per group give blocks
-  three or four tiles -- both counter parities and the record array reused
+  filter: tiles are dealt to 8 groups and a group's to a quarter of the
+  resident blocks (64), so 200 tiles per group give blocks three or four
+  tiles -- both counter parities and the record array reused
   while the copy-out of the tile before is in flight;
 - one id repeated over whole tiles (11 slices take 1024 records each, the
   largest rank a counter hands out), an all-invalid and an all-valid batch;

@@ -1,5 +1,5 @@
-"""The segmented PFADD (sketch_part.hip k_seg_c1 / k_seg_da (or k_seg_scan + k_seg_d) /
-k_seg_e): pass C of the one-link partitioned K1 when a batch's register
+"""The segmented PFADD (sketch_seg.hip k_seg_c1 / k_seg_da / k_seg_e /
+k_seg_m): pass C of the one-link partitioned K1 when a batch's register
 updates are dense in the slab -- valid swipes' (register, rank) records
 bucketed by key, each window of keys staged in LDS, raised there and its
 risen lines stored back.  The result must equal the sequential hllAdd()s of
@@ -117,7 +117,7 @@ def test_seg_key_counts(engine, orc, nkeys, n, klog):
 @pytest.mark.parametrize("nkeys,klog", [(4097, 1), (20_000, 3), (300, 0)])
 def test_seg_all_valid_runs(engine, orc, nkeys, klog):
     """Every swipe valid (no invalid ids): a full C1 run holds 8192 records,
-    so the arena form's 4-record pads no longer fit its LDS and it takes the
+    so the arena's 4-record pads no longer fit its LDS and it takes the
     unpadded layout, storing each bucket's pad itself (k_seg_c1)."""
     from rtsas_amd import synthetic
     from rtsas_amd.engine import DeviceBuffer
@@ -155,7 +155,7 @@ def _pack(items):
 def test_seg_ragged_ids_hot_key(engine, orc):
     """0..40-byte ids (pass A's generic hash), one key taking 60 % of the
     swipes (a bucket whose runs fill whole chunks), C3's one-link filter.
-    In the arena form the hot key's bucket holds ~12 chunks against kstat = 6
+    In the arena the hot key's bucket holds ~12 chunks against kstat = 6
     fixed slots per bucket (16 buckets, 22 chunks): its later chunks take
     counted slots through the chunk table."""
     import ctypes as C

@@ -2,7 +2,7 @@
 # Build libsketch.so from the WORKING TREE with extra compile flags into
 # tools/ab/libsketch_<name>.so (A/B of compile-time variants on one GPU box:
 # SKE_LIB=tools/ab/libsketch_<name>.so python bench.py ...).
-# usage: bash tools/ab_variant.sh <name> "-DSKE_PB_SPLIT=1 ..."
+# usage: bash tools/ab_variant.sh <name> "-DSKE_NT=7 ..."
 set -e
 name=$1; extra=$2
 root=$(git rev-parse --show-toplevel)
