@@ -6,6 +6,7 @@
 #pragma once
 #include "sketch_common.h"
 #include "sketch_internal.h"
+#include "sketch_seg_plan.h"
 
 namespace ske {
 
@@ -163,7 +164,8 @@ constexpr uint32_t kSegRunTiles = kPbGroup;                 // tiles per level-1
 constexpr uint32_t kSegRunSw = kSegRunTiles * kTileFl;      // 8192 swipes
 constexpr uint32_t kSegMaxB1 = 512;                         // level-1 buckets
 constexpr uint32_t kSegMaxWpb = 512;                        // windows per bucket
-constexpr uint32_t kSegChunk = 8192;                        // records per level-2 chunk
+// (kSegChunk, 8192 records per level-2 chunk: sketch_seg_plan.h)
+static_assert(kSegRunSw == kSegRun, "sketch_seg_plan.h sizes the arena for runs of kSegRunSw swipes");
 constexpr uint32_t kSegMaxRuns = kPSub / kSegRunSw;         // 8192 runs per sub-batch
 constexpr uint32_t kSegRecShift = 20;                       // record: slot-in-bucket above bit 20
 static_assert(kSegMaxRuns < 65536, "k_seg_c1's uint16 mark epochs (run + 1) would wrap");
@@ -197,11 +199,7 @@ struct SegArgs {
     uint32_t kmaxc;   // chunks a bucket can have in a sub-batch
     uint32_t kstat;   // chunk c < kstat of bucket h sits in slot h * kstat + c; later chunks take
                       // slots nb1 * kstat + (counter), named in ctab
-};
-
-// the segmented PFADD's geometry for one batch (seg_plan)
-struct SegPlan {
-    uint32_t s1, b1, wlog, klog, nb1, nwin, maxch, nsub, dense_min;
+    unsigned int *err;  // the call's error word (D: bit 8, more chunks than maxch rows)
 };
 
 // the fail-list instantiation: one link of k = 11 (C3/C5's filter), slice

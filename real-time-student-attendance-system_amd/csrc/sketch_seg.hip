@@ -38,6 +38,7 @@
 #include <type_traits>
 
 #include "sketch_part.h"
+#include "sketch_seg_plan.h"
 
 namespace ske {
 
@@ -345,13 +346,21 @@ __global__ void __launch_bounds__(T, SegDA<T>::WPE) k_seg_da(const SegArgs S) {
         t = fl[tid * kSegFillStride];
         tot[tid] = t;
     }
-    uint32_t nq;
-    const uint32_t cbase = seg_scan(tid < S.nb1 ? (t + kSegChunk - 1) / kSegChunk : 0u, ws, nq);
+    uint32_t nqa;
+    const uint32_t cbase = seg_scan(tid < S.nb1 ? (t + kSegChunk - 1) / kSegChunk : 0u, ws, nqa);
+    // The sub-batch's region has maxch rows, which seg_rows_max
+    // (sketch_seg_plan.h) proves enough for any input; were there more chunks
+    // all the same, the rows stop at maxch (no row and no chunk base leaves
+    // the region) and error bit 8 is set, reported as the call's error.
+    const uint32_t nq = nqa < S.maxch ? nqa : S.maxch;
     if (tid < S.nb1) {
         cbl[tid] = cbase;
-        if (blockIdx.x == 0) S.cb[size_t(S.s) * (S.nb1 + 1) + tid] = cbase;
+        if (blockIdx.x == 0) S.cb[size_t(S.s) * (S.nb1 + 1) + tid] = cbase < S.maxch ? cbase : S.maxch;
     }
-    if (tid == 0 && blockIdx.x == 0) S.cb[size_t(S.s) * (S.nb1 + 1) + S.nb1] = nq;
+    if (tid == 0 && blockIdx.x == 0) {
+        S.cb[size_t(S.s) * (S.nb1 + 1) + S.nb1] = nq;
+        if (nqa > S.maxch) atomicOr(S.err, 8u);
+    }
     lds_barrier();
     uint32_t *r2 = S.r2 + size_t(S.s) * S.maxch * kSegChunk;
     uint32_t *o2 = S.o2 + size_t(S.s) * S.maxch * (wpb + 1);
@@ -781,56 +790,7 @@ __global__ void __launch_bounds__(1024) k_seg_m(const PartArgs A, const SegArgs 
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-// The segmented PFADD's geometry for a slab of nslots keys and a batch of n
-// swipes in sub-batches of `sub`: windows of 2^klog keys (W = slot >> klog);
-// 2^b1 level-1 buckets of 2^wlog windows each, window W in bucket W mod
-// 2^b1 (buckets interleave windows, so the consecutive windows of a hot
-// lecture's day keys fall in different buckets and every bucket carries
-// about the same records), b1 + wlog = ceil(log2(windows)) split evenly so
-// that both levels' runs stay long; false when the slab needs more than 2^9
-// buckets of 2^9 windows.
-static bool seg_plan(uint32_t nslots, uint64_t n, uint32_t sub, const SegOpts &so, SegPlan *P) {
-    if (nslots == 0 || n == 0 || so.klog < 0 || so.klog > 3) return false;
-    const uint32_t klog = uint32_t(so.klog);
-    const uint32_t nwin = uint32_t((uint64_t(nslots) + (1u << klog) - 1) >> klog);
-    uint32_t tb = 0;
-    while ((uint64_t(1) << tb) < nwin) tb++;
-    // windows per bucket 2^wlog: at least half the window bits, and at least
-    // tb - 5 (2^25 sub-batches: level-2 sorts over more windows beat longer
-    // level-1 segments up to 2^9; profiles/r05_ab_seg_b1.txt: b1 7 at C3's
-    // 2^16 windows, 5 at the 8-way shard's 2^13)
-    uint32_t wlog = std::max((tb + 1) / 2, tb > 5 ? tb - 5 : 0u), b1 = tb - wlog;
-    if (wlog > 9) {
-        wlog = 9;
-        b1 = tb - 9;
-    }
-    if (so.b1 >= 0) {  // the option: level-1 buckets 2^b1 (windows per bucket 2^(tb - b1) <= 2^9)
-        b1 = uint32_t(so.b1) < tb ? uint32_t(so.b1) : tb;
-        wlog = tb - b1;
-    }
-    if (b1 > 9) {
-        b1 = 9;
-        wlog = tb - 9;
-    }
-    if (wlog > 9) return false;
-    P->klog = klog;
-    P->wlog = wlog;
-    P->b1 = b1;
-    P->s1 = klog + wlog;
-    P->nwin = nwin;
-    P->nb1 = 1u << b1;
-    P->maxch = (sub + kSegChunk - 1) / kSegChunk + P->nb1;
-    // sub-batches per window pass: at most 64, and their level-2 records
-    // within a 2^31-byte buffer range (the window pass's record loads); a
-    // batch of more runs a window pass after every nsub of them
-    const uint64_t kmax = ((uint64_t(1) << 29) - 1) / (uint64_t(P->maxch) * kSegChunk);
-    const uint64_t ns = (n + sub - 1) / sub;
-    if (kmax == 0) return false;
-    P->nsub = uint32_t(std::min<uint64_t>(std::min<uint64_t>(ns, kmax), 64));
-    const uint64_t dm = uint64_t(so.dense_min_x100) * ((uint64_t(1) << klog) * (kHllRegs / 128)) / 100;
-    P->dense_min = dm < 1 ? 1u : (dm > 0xffffffffu ? 0xffffffffu : uint32_t(dm));
-    return true;
-}
+// (the geometry, seg_plan, and the slot sizing, seg_slots: sketch_seg_plan.h)
 
 // segmented for this batch: the fail-list chain, the option, and (auto) at
 // least density_x100 / 100 swipes per 128-B register line of the slab
@@ -849,25 +809,20 @@ bool seg_use(const PartArgs &A, const SegOpts &so, uint32_t nslots, uint64_t n, 
 // the segmented PFADD's scratch (context slots 32, 36-43 and 45; 33-35, the
 // run-table form's until round 8, are free)
 hipError_t seg_scratch(const SegPlan &P, uint32_t sub, uint64_t n, Scratch *scr, SegArgs *S) {
-    const uint64_t m = n < sub ? n : sub;
     const uint64_t mg = std::min<uint64_t>(n, uint64_t(P.nsub) * sub);  // swipes of one window pass
     hipError_t e = hipSuccess;
-    // chunk slots: about twice a bucket's mean fixed per bucket, and as
-    // many counted ones as the sub-batch could ever need (every bucket's
-    // last chunk may be partial); slot numbers < 2^14 (k_seg_c1's packing)
-    const uint64_t ch = (m + kSegChunk - 1) / kSegChunk, dyn = ch + P.nb1;
-    uint64_t kst = 2 * ((ch + P.nb1 - 1) / P.nb1) + 2;
-    kst = std::min<uint64_t>(kst, ((1u << 14) - 1 - dyn) / P.nb1);
-    S->kstat = uint32_t(kst);
-    S->kmaxc = uint32_t(ch + 1);
-    S->r1 = (uint32_t *)scratch_get(scr, 32, size_t(P.nb1 * kst + dyn) * kSegChunk * 4, &e);
+    // chunk slots and rows: seg_slots (sketch_seg_plan.h)
+    const SegSlots L = seg_slots(P, sub, n);
+    S->kstat = L.kstat;
+    S->kmaxc = L.kmaxc;
+    S->r1 = (uint32_t *)scratch_get(scr, 32, size_t(L.r1_slots) * kSegChunk * 4, &e);
     if (e == hipSuccess)
         S->fill = (uint32_t *)scratch_get(scr, 40, size_t(P.nsub) * (P.nb1 + 1) * kSegFillStride * 4, &e);
     if (e == hipSuccess) S->ctab = (uint32_t *)scratch_get(scr, 41, size_t(P.nb1) * S->kmaxc * 4, &e);
     if (e == hipSuccess)
-        S->r2 = (uint32_t *)scratch_get(scr, 36, size_t(P.nsub) * P.maxch * kSegChunk * 4, &e);
+        S->r2 = (uint32_t *)scratch_get(scr, 36, size_t(L.rows) * kSegChunk * 4, &e);
     if (e == hipSuccess)
-        S->o2 = (uint32_t *)scratch_get(scr, 37, size_t(P.nsub) * P.maxch * ((1u << P.wlog) + 1) * 4, &e);
+        S->o2 = (uint32_t *)scratch_get(scr, 37, size_t(L.rows) * ((1u << P.wlog) + 1) * 4, &e);
     if (e == hipSuccess) S->cb = (uint32_t *)scratch_get(scr, 38, size_t(P.nsub) * (P.nb1 + 1) * 4, &e);
     // the window pass's cut windows: a cut window has > slice records and
     // ceil(records / slice) < 2 records / slice slices, so 2 n / slice
@@ -895,6 +850,7 @@ hipError_t launch_seg_sub(const PartArgs &A, SegArgs &S, const SegPlan &P, uint3
                           PassHook hook, void *hook_user) {
     if (hook) hook(hook_user, 2, 0, st);
     S.s = si % P.nsub;
+    S.err = A.err;
     S.nruns = (A.ntiles + kSegRunTiles - 1) / kSegRunTiles;
     if (S.s == 0) {
         // the group's fill counts, and the chunk table (D clears what C1

@@ -92,9 +92,11 @@ def test_seg_forced_small(engine, orc, klog, dense_min, sub):
                                            (20_000, 700_001, 0), (3, 9_000_000, 0), (4097, 700_001, 1)])
 def test_seg_key_counts(engine, orc, nkeys, n, klog):
     """Slabs of 1 key (one bucket, one window), 9 (a partial window), 4097
-    (a partial last bucket) and 20 000 (512-bucket cap: s1 grows), uniform
-    keys, forced on; one key under 12 M swipes (a window of > 1024 runs --
-    staged in batches -- cut into ~165 slices), three under 9 M."""
+    (a partial last bucket) and 20 000 (the auto plan's 32 buckets at klog 3,
+    64 buckets of 2^9 windows at klog 0; the 512-bucket cap is reached in
+    test_seg_capacity.py), uniform keys, forced on; one key under 12 M
+    swipes (a window of > 1024 runs -- staged in batches -- cut into ~165
+    slices), three under 9 M."""
     from rtsas_amd import synthetic
     from rtsas_amd.engine import DeviceBuffer
     w = synthetic.WORKLOADS["c3"]
