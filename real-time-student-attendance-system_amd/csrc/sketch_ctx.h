@@ -1,0 +1,227 @@
+// sketch_ctx.h -- the context and what the sketch_api_*.cpp units share.
+//
+// The C-ABI of include/sketch.h is split by subsystem:
+//   sketch_api_ctx.cpp     lifecycle, options, the error word, streams, staging,
+//                          pass timing, the scratch-use ordering, graphs
+//   sketch_api_bloom.cpp   link geometry, chain growth, export / import,
+//                          BF.MEXISTS and BF.MADD
+//   sketch_api_hll.cpp     the register slab, PFADD, PFCOUNT, PFMERGE, export / import
+//   sketch_api_swipes.cpp  K1: variant choice, launch_k1, ske_swipes*, ske_route_*
+//   sketch_api_ingest.cpp  ingest, the key table, the generator
+// A helper used by one unit is static there; what crosses units is declared here.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/sketch.h"
+#include "sketch_common.h"
+#include "sketch_internal.h"
+
+// pass kinds of ske_pass_times: 0 a single-kernel K1 (LDS / global /
+// XCD-partitioned), 1-3 the partitioned K1's passes A, B, C
+constexpr int kPassKinds = SKE_PASS_KINDS;
+
+namespace ske {
+
+struct Link {
+    uint8_t *bf = nullptr;  // device
+    uint64_t entries = 0, bytes = 0, bits = 0, size = 0;
+    double error = 0, bpe = 0;
+    int hashes = 0;
+    Divisor div{};
+};
+
+struct Filter {
+    bool exists = false;
+    bool dev_ok = false;  // `dev` matches `links`
+    ChainDev dev{};       // cached kernel view of the chain (rebuilt on growth)
+    std::vector<Link> links;
+    uint64_t size = 0;
+    uint32_t growth = 2;
+    bool nonscaling = false;
+};
+
+struct Staged {
+    const uint8_t *bytes = nullptr;
+    const uint32_t *offs = nullptr;
+};
+
+// The last use of one ordering group of context scratch slots (ScratchSlot,
+// sketch_internal.h): a use on another stream first waits for it (ScratchUser).
+struct ScratchUse {
+    hipEvent_t done = nullptr;
+    hipStream_t stream = nullptr;
+    unsigned long long cap = 0;  // capture id of stream's last scratch use (0: none)
+    bool pending = false;        // that use is not yet covered by done (recorded lazily)
+};
+
+}  // namespace ske
+
+struct ske_ctx {
+    int device = 0;
+    int cus = 256;
+    hipStream_t own = nullptr;
+    hipStream_t st = nullptr;
+    std::vector<ske::Filter> filters;
+    uint8_t *regs = nullptr;  // nslots * 16384
+    uint32_t nslots = 0;
+    double *tau = nullptr, *sig = nullptr;  // device estimator tables (lazy)
+    ske::Scratch *scratch = nullptr;
+    // staging buffers by use (grow on demand)
+    void *stg[ske::kStageSlotCount] = {};
+    size_t stg_cap[ske::kStageSlotCount] = {};
+    ske::HostStager *hs = nullptr;  // pinned double buffer + copy threads for pageable inputs (lazy)
+    unsigned int *err = nullptr;  // [0] sticky slot-error word; see check_call_err
+    bool err_pending = false;     // taken from the device, not yet reported by ske_sync
+    unsigned long long *stats = nullptr;
+    int pb = 2;           // K1 tile: swipes per thread in flight (1, 2, 4, 8)
+    int variant = -1;     // -1 auto, 0 global, 1 LDS, 2 XCD-partitioned, 3 partitioned
+    uint32_t part_sub = 0;  // partitioned K1: swipes per sub-batch (0: default)
+    ske::SegOpts seg;       // partitioned K1: the segmented PFADD's options
+    bool lds_ok = false;
+    bool k1_ok = false;       // short-id LDS K1 (sketch_k1.hip) usable
+    int k1_grid = 0;          // blocks of the short-id LDS K1 (0: one per CU)
+    int k1_persistent = 1;    // ske_swipes_many_async: one LDS K1 launch over all batches
+    uint8_t *zero16 = nullptr;  // 16 zero bytes on the device
+    // the XCD-partitioned and partitioned K1 and routing keep per-launch state
+    // in the context scratch: a launch on another stream first waits for the
+    // previous one of its group (ScratchSlot's ordering rule, sketch_internal.h)
+    ske::ScratchUse xr;  // K1's slots (kScrXr, kScrPart*, kScrSeg*)
+    ske::ScratchUse rt;  // routing's slots (kScrRoute*): ordered among routing calls, not behind K1
+    // executable graphs alive (recorded, not yet freed): they hold pointers to
+    // the scratch and the register slab, so neither may be reallocated
+    int live_graphs = 0;
+    bool capturing = false;
+    // scratch users recorded into the graph being captured (bit 0: xr,
+    // bit 1: rt), and per live graph the users its replays hold: a replay
+    // records only their events, so a graph without routing does not order
+    // the next routing call behind itself
+    unsigned cap_users = 0;
+    std::unordered_map<void *, unsigned> graph_users;
+    // pass timing (option "pass_timing"): HIP event pairs around every K1
+    // kernel, recorded on the stream the kernel runs on (never inside a
+    // capture); ske_pass_times() sums them per pass
+    bool timing = false;
+    std::vector<hipEvent_t> ev_pool;
+    struct Mark { int pass; hipEvent_t a, b; bool own_a; };  // pass < 0: void (an abandoned mark)
+    std::vector<Mark> marks;
+    double pass_ms[kPassKinds] = {};
+    uint64_t pass_n[kPassKinds] = {};
+    // ske_swipes_many_async: side streams of the fork/join branches (lazy)
+    hipStream_t many_st[SKE_MANY_MAX_BRANCHES - 1] = {};
+    hipEvent_t many_join[SKE_MANY_MAX_BRANCHES - 1] = {};
+    hipEvent_t many_fork = nullptr;
+    int many_n = 0;
+    // host-fed chunk pipeline (ske_swipes_fixed_bits): a copy stream and one
+    // event per chunk in flight (lazy)
+    hipStream_t copy_st = nullptr;
+    std::vector<hipEvent_t> chunk_ev;
+    // ingest key table (open addressing on the 128-bit key hash)
+    uint64_t *kt_key = nullptr;  // 2 per entry, kh0 == 0: empty
+    uint32_t *kt_slot = nullptr;
+    uint64_t kt_cap = 0, kt_count = 0;
+    std::string last_hip;
+};
+
+#define HIPCHK(ctx, expr)                                                                         \
+    do {                                                                                          \
+        hipError_t _e = (expr);                                                                   \
+        if (_e != hipSuccess) {                                                                   \
+            (ctx)->last_hip = std::string(#expr) + ": " + hipGetErrorString(_e);                  \
+            return SKE_EHIP;                                                                      \
+        }                                                                                         \
+    } while (0)
+
+namespace ske {
+
+// ---- sketch_api_ctx.cpp
+
+// staging buffer `slot` of at least `bytes` (nullptr and *rc set on failure)
+void *stage_buf(ske_ctx *c, StageSlot slot, size_t bytes, int *rc);
+// Items to device.  SKE_MEM_DEVICE pointers are used in place; host items are
+// copied as the byte range [offs[0], offs[n]) plus offsets, and the device
+// bytes pointer is rebased so that offs[] index it unchanged.
+int stage_items(ske_ctx *c, const uint8_t *bytes, const uint32_t *offs, uint64_t n, int mem, Staged *out);
+int stage_u32(ske_ctx *c, const uint32_t *p, uint64_t n, int mem, StageSlot slot, const uint32_t **out);
+
+// One pass-timing mark: the event pair around what is enqueued on `st`
+// between begin() and end().  Inert when not timing, or capturing.  No exit
+// leaves a mark half-recorded: the destructor of a guard not yet ended (an
+// error return) records the end event and voids the mark with every mark
+// begun after it (those of the failed scope), so ske_pass_times recycles their
+// events and counts none -- a failed host-fed call contributes nothing.
+class PassMark {
+public:
+    PassMark() = default;
+    PassMark(ske_ctx *c, int pass, hipStream_t st) { begin(c, pass, st); }
+    PassMark(const PassMark &) = delete;
+    PassMark &operator=(const PassMark &) = delete;
+    ~PassMark() { abandon(); }
+    // `start`: an end event just recorded on st with nothing enqueued since
+    // (the previous kernel's), reused as this mark's start: one marker packet fewer
+    void begin(ske_ctx *c, int pass, hipStream_t st, hipEvent_t start = nullptr);
+    void end();  // records the end event; the mark counts
+    hipEvent_t end_event() const { return b_; }  // once ended (nullptr when inert)
+
+private:
+    void abandon();
+    ske_ctx *c_ = nullptr;
+    hipEvent_t b_ = nullptr;
+    hipStream_t st_ = nullptr;
+    size_t idx_ = 0;     // of this mark in c_->marks (which only grows while a guard lives)
+    bool open_ = false;  // begun, end event not yet recorded
+};
+
+// One use of an ordering group of the context scratch (c->xr or c->rt) by what
+// is enqueued on `st` while the guard lives: the constructor makes st wait for
+// the group's last use on another stream (rc != 0: it failed, nothing may be
+// launched), the destructor notes this use on every exit after that.
+//
+// The wait only links launches of the same capture (or of none): an event
+// recorded outside a capture cannot be waited on inside it, nor the reverse
+// (the caller synchronises before recording a graph, as engine.capture does;
+// ske_graph_launch records the event after a replay).
+class ScratchUser {
+public:
+    ScratchUser(ske_ctx *c, ScratchUse &u, hipStream_t st);
+    ~ScratchUser();
+    ScratchUser(const ScratchUser &) = delete;
+    ScratchUser &operator=(const ScratchUser &) = delete;
+    int rc = SKE_OK;
+
+private:
+    ske_ctx *c_;
+    ScratchUse &u_;
+    hipStream_t st_;
+    unsigned long long cid_ = 0;
+};
+
+// scratch that cannot grow (a graph is being recorded, or alive) -> SKE_EBUSY
+int scratch_error(ske_ctx *c, hipError_t e);
+
+inline Filter *get_filter(ske_ctx *c, uint32_t fid) { return fid < c->filters.size() ? &c->filters[fid] : nullptr; }
+
+// the sticky slot-error word around a synchronous call (see k_err_begin)
+int err_begin(ske_ctx *c);
+int check_call_err(ske_ctx *c);
+
+// ---- sketch_api_bloom.cpp
+void free_filter(Filter &F);
+// the kernel view of F's chain (cached; the empty chain for a missing key)
+const ChainDev &chain_of(Filter *F);
+
+// ---- sketch_api_swipes.cpp
+bool use_lds(const ske_ctx *c, const ChainDev &ch);
+// The short-id LDS kernel (sketch_k1.hip) when the chain, the batch and the
+// options allow it; false: use the generic kernels.
+bool k1_fast_args(ske_ctx *c, const ChainDev &ch, const PartBatch &b, K1Args *A);
+// blocks of the short-id LDS K1: option "k1_grid", or one per CU
+inline int k1_grid(const ske_ctx *c) { return c->k1_grid ? c->k1_grid : c->cus; }
+// Enqueue K1 (mode swipes) over b on st with the variant the chain selects;
+// `grid`: blocks of the short-id LDS K1
+int launch_k1(ske_ctx *c, const ChainDev &ch, const PartBatch &b, hipStream_t st, int grid);
+
+}  // namespace ske

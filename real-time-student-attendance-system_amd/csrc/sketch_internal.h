@@ -185,7 +185,91 @@ hipError_t launch_swipes_part(const ChainDev &ch, const PartBatch *bt, uint32_t 
 // sketch_order.hip -- order-exact paths (replies that depend on item order)
 struct Scratch;  // growable device scratch, owned by the context
 constexpr int kScratchSlots = 48;
-void *scratch_get(Scratch *s, int slot, size_t bytes, hipError_t *err);
+
+// Every slot of the context scratch, by owner (who sizes it) and user.  The
+// numbers carry no meaning beyond identity; a slot belongs to exactly one of
+// three ordering groups:
+//   sync  used only inside synchronous calls, which run on the context stream
+//         and end with a stream synchronise, so two such calls never overlap;
+//   xr    K1's per-launch state, ordered through ske_ctx::xr (ScratchUser);
+//   rt    routing's, ordered through ske_ctx::rt.
+// The rule: a slot reachable from an rt-ordered call may have no user ordered
+// through xr, and the other way round -- routing runs beside K1 on another
+// stream (distributed.SwipeExchange's pipelined form), and neither waits for
+// the other.  Slots shared on purpose are one enumerator naming both users.
+enum ScratchSlot : int {
+    // -- sync
+    kScrKeysOrFirst,   // pfadd_exact: sort keys | ske_bf_madd: a link's first-setter table
+                       // (up to 4 x bits bytes); both synchronous calls, never at once
+    kScrKeysSorted,    // pfadd_exact (sketch_order.hip): sorted keys,
+    kScrVals,          //   element indices,
+    kScrValsSorted,    //   sorted indices,
+    kScrRank,          //   ranks,
+    kScrRankSorted,    //   ranks in sorted order,
+    kScrPrefMax,       //   running maximum per register,
+    kScrSortTmp,       //   rocprim radix sort temporary,
+    kScrScanKeyTmp,    //   rocprim scan-by-key temporary
+    kScrScanTmp,       // scan_inclusive_u32's rocprim temporary: ske_bf_madd, ske_keytab_lookup,
+                       // ske_ingest_swipes (synchronous calls, never at once)
+    kScrBfHa,          // ske_bf_madd: item hashes a,
+    kScrBfHb,          //   hashes b,
+    kScrBfState,       //   candidate state,
+    kScrBfRes,         //   replies,
+    kScrBfAbsent,      //   absent flags,
+    kScrBfPos,         //   their prefix count
+    kScrMergePartial,  // ske_hll_pfmerge over > 256 sources: partial maxima
+    kScrKtFlag,        // key table lookup (ske_keytab_lookup, ske_ingest_swipes): found flags,
+    kScrKtLen,         //   id lengths of found keys
+    kScrKtIncl,        // ske_keytab_lookup: prefix count of the flags
+    kScrInSlot,        // ske_ingest_swipes: slot per message,
+    kScrInFlagIncl,    //   prefix count of the flags,
+    kScrInLenIncl,     //   prefix sum of the id lengths,
+    kScrInIds,         //   packed ids,
+    kScrInOffs,        //   their offsets,
+    kScrInKslot,       //   their slots,
+    kScrInKvalid,      //   K1's answers
+    // -- xr
+    kScrXr,            // launch_k1: the XCD-partitioned K1's state (sketch_xr.hip)
+    kScrPartRec,       // part_scratch (sketch_part.hip): probe records,
+    kScrPartOff,       //   run boundaries,
+    kScrPartFail,      //   fail bytes (chains without fail lists),
+    kScrPartHllw,      //   HLL words,
+    kScrPartFlist,     //   fail lists of one-link chains
+    kScrSegR1,         // seg_scratch (sketch_seg.hip): level-1 chunk arena,
+    kScrSegFill,       //   fill counts,
+    kScrSegCtab,       //   chunk table,
+    kScrSegR2,         //   level-2 chunk rows,
+    kScrSegO2,         //   their window offsets,
+    kScrSegCb,         //   chunk bases,
+    kScrSegQ,          //   the window pass's queue word,
+    kScrSegQitems,     //   queue entries,
+    kScrSegMlist,      //   cut windows,
+    kScrSegCopies,     //   their window copies
+    // -- rt
+    kScrRouteHist,     // ske_route_swipes, ske_route_swipes_cap_async: per-block histogram,
+    kScrRouteTot,      // ske_route_swipes: the owners' totals
+    kScratchSlotCount
+};
+static_assert(kScratchSlotCount <= kScratchSlots, "Scratch holds kScratchSlots slots");
+
+// The context's staging buffers (ske_ctx::stg) by use; every user is a
+// synchronous call on the context stream.
+enum StageSlot : int {
+    kStgBytes,     // item bytes (stage_items; the fixed-width ids of ske_swipes_fixed*)
+    kStgOffs,      // item offsets (stage_items)
+    kStgSlots,     // a slot per item
+    kStgOut,       // per-item replies on their way to the host (answers, changed flags, packed bits)
+    kStgAnswers,   // ske_swipes_fixed_bits: answer bytes before packing
+    kStgReply,     // small replies: PFCOUNT results, a histogram, a dense export
+    kStgList,      // a slot list (PFCOUNT / PFMERGE) or key hashes (ske_keytab_insert)
+    kStgList2,     // group offsets (PFCOUNT) or key slots (ske_keytab_insert)
+    kStgCheck,     // the device slot-range check word (check_slots_dev)
+    kStageSlotCount
+};
+
+Scratch *scratch_new();
+void scratch_delete(Scratch *s);
+void *scratch_get(Scratch *s, ScratchSlot slot, size_t bytes, hipError_t *err);
 void scratch_set_recording(Scratch *s, bool on);  // slots handed out now get pinned
 void scratch_unpin(Scratch *s);                    // every graph freed: slots may grow
 
@@ -214,6 +298,9 @@ hipError_t launch_bf_resolve(const LinkDev &L, uint64_t n, const uint64_t *ha, c
                              uint8_t *state, const uint32_t *absent, const uint32_t *pos,
                              uint32_t cap, int8_t *res, uint8_t *bf_mut, int cus,
                              hipStream_t st);
+// counter[0] += items with state == 0 (candidates not yet resolved)
+hipError_t launch_bf_count_cands(uint64_t n, const uint8_t *state, unsigned long long *counter,
+                                 int cus, hipStream_t st);
 // mark every remaining candidate with a result code (non-scaling full)
 hipError_t launch_bf_fill_rest(uint64_t n, uint8_t *state, int8_t *res, int8_t code, int cus,
                                hipStream_t st);

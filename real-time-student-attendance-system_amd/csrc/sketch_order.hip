@@ -36,7 +36,7 @@ void scratch_unpin(Scratch *s) {
 // with hipErrorStreamCaptureUnsupported (the allocation would be prohibited
 // inside a capture, and the hipFree would release memory that recorded nodes
 // still point to).
-void *scratch_get(Scratch *s, int slot, size_t bytes, hipError_t *err) {
+void *scratch_get(Scratch *s, ScratchSlot slot, size_t bytes, hipError_t *err) {
     if (bytes == 0) bytes = 16;
     if (s->recording) s->pinned[slot] = true;
     if (s->cap[slot] < bytes && s->pinned[slot]) {
@@ -155,13 +155,13 @@ hipError_t pfadd_exact(Scratch *s, const uint32_t *slot, const uint8_t *bytes,
                        uint8_t *changed_dev, unsigned int *err_dev, int cus, hipStream_t st) {
     if (n == 0) return hipSuccess;
     hipError_t e = hipSuccess;
-    uint64_t *keys = (uint64_t *)scratch_get(s, 0, n * 8, &e);
-    uint64_t *keys_s = (uint64_t *)scratch_get(s, 1, n * 8, &e);
-    uint32_t *vals = (uint32_t *)scratch_get(s, 2, n * 4, &e);
-    uint32_t *vals_s = (uint32_t *)scratch_get(s, 3, n * 4, &e);
-    uint8_t *rank = (uint8_t *)scratch_get(s, 4, n, &e);
-    uint8_t *rank_s = (uint8_t *)scratch_get(s, 5, n, &e);
-    uint8_t *pref = (uint8_t *)scratch_get(s, 6, n, &e);
+    uint64_t *keys = (uint64_t *)scratch_get(s, kScrKeysOrFirst, n * 8, &e);
+    uint64_t *keys_s = (uint64_t *)scratch_get(s, kScrKeysSorted, n * 8, &e);
+    uint32_t *vals = (uint32_t *)scratch_get(s, kScrVals, n * 4, &e);
+    uint32_t *vals_s = (uint32_t *)scratch_get(s, kScrValsSorted, n * 4, &e);
+    uint8_t *rank = (uint8_t *)scratch_get(s, kScrRank, n, &e);
+    uint8_t *rank_s = (uint8_t *)scratch_get(s, kScrRankSorted, n, &e);
+    uint8_t *pref = (uint8_t *)scratch_get(s, kScrPrefMax, n, &e);
     if (e != hipSuccess) return e;
     const unsigned grid = grid_for(n, 256, cus * 16);
     hipLaunchKernelGGL(k_hll_prep, dim3(grid), dim3(256), 0, st, slot, bytes, offs, n, nslots,
@@ -171,7 +171,7 @@ hipError_t pfadd_exact(Scratch *s, const uint32_t *slot, const uint8_t *bytes,
     size_t tb = 0;
     e = rocprim::radix_sort_pairs(nullptr, tb, keys, keys_s, vals, vals_s, n, 0u, end_bit, st);
     if (e != hipSuccess) return e;
-    void *tmp = scratch_get(s, 7, tb, &e);
+    void *tmp = scratch_get(s, kScrSortTmp, tb, &e);
     if (e != hipSuccess) return e;
     e = rocprim::radix_sort_pairs(tmp, tb, keys, keys_s, vals, vals_s, n, 0u, end_bit, st);
     if (e != hipSuccess) return e;
@@ -180,7 +180,7 @@ hipError_t pfadd_exact(Scratch *s, const uint32_t *slot, const uint8_t *bytes,
     e = rocprim::exclusive_scan_by_key(nullptr, tb2, keys_s, rank_s, pref, uint8_t(0), size_t(n),
                                        MaxU8(), rocprim::equal_to<uint64_t>(), st);
     if (e != hipSuccess) return e;
-    tmp = scratch_get(s, 8, tb2, &e);
+    tmp = scratch_get(s, kScrScanKeyTmp, tb2, &e);
     if (e != hipSuccess) return e;
     e = rocprim::exclusive_scan_by_key(tmp, tb2, keys_s, rank_s, pref, uint8_t(0), size_t(n),
                                        MaxU8(), rocprim::equal_to<uint64_t>(), st);
@@ -361,7 +361,7 @@ hipError_t scan_inclusive_u32(Scratch *s, const uint32_t *in, uint32_t *out, uin
     size_t tb = 0;
     hipError_t e = rocprim::inclusive_scan(nullptr, tb, in, out, size_t(n), rocprim::plus<uint32_t>(), st);
     if (e != hipSuccess) return e;
-    void *tmp = scratch_get(s, 9, tb, &e);
+    void *tmp = scratch_get(s, kScrScanTmp, tb, &e);
     if (e != hipSuccess) return e;
     return rocprim::inclusive_scan(tmp, tb, in, out, size_t(n), rocprim::plus<uint32_t>(), st);
 }

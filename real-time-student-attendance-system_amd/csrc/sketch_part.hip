@@ -1223,7 +1223,7 @@ static bool part_glayout(PartArgs *A, const SegOpts &so, uint32_t ntiles_max) {
 }
 
 // the scratch of a sub-batch of up to `sub` swipes (context scratch slots
-// 28-31 and 44: probe records, run boundaries, fail bytes, HLL words, and the
+// kScrPart*: probe records, run boundaries, fail bytes, HLL words, and the
 // fail lists of one-link chains)
 static hipError_t part_scratch(PartArgs *A, uint64_t n, uint32_t sub, const SegOpts &so, Scratch *scr) {
     const uint32_t m = n < sub ? uint32_t(n) : sub;
@@ -1233,18 +1233,18 @@ static hipError_t part_scratch(PartArgs *A, uint64_t n, uint32_t sub, const SegO
     A->off_stride = (ntiles_max + 15) & ~15u;
     hipError_t e = hipSuccess;
     part_glayout(A, so, ntiles_max);
-    A->rec = (uint32_t *)scratch_get(scr, 28, (size_t(A->govf) + size_t(ntiles_max) * A->stride) * 4, &e);
-    if (e == hipSuccess) A->off = (uint32_t *)scratch_get(scr, 29, size_t(A->off_stride) * (A->nslices + 1) * 4, &e);
+    A->rec = (uint32_t *)scratch_get(scr, kScrPartRec, (size_t(A->govf) + size_t(ntiles_max) * A->stride) * 4, &e);
+    if (e == hipSuccess) A->off = (uint32_t *)scratch_get(scr, kScrPartOff, size_t(A->off_stride) * (A->nslices + 1) * 4, &e);
     // (fail bytes: the fail-list chains keep their overflow flags in the HLL words)
     A->fail = nullptr;
     if (e == hipSuccess && !part_flist(*A))
-        A->fail = (uint8_t *)scratch_get(scr, 30, size_t(fstride) * A->nlinks, &e);
-    if (e == hipSuccess) A->hllw = (uint32_t *)scratch_get(scr, 31, size_t(m) * 4, &e);
+        A->fail = (uint8_t *)scratch_get(scr, kScrPartFail, size_t(fstride) * A->nlinks, &e);
+    if (e == hipSuccess) A->hllw = (uint32_t *)scratch_get(scr, kScrPartHllw, size_t(m) * 4, &e);
     A->fail_stride = fstride;
     A->fl_stride = A->off_stride;
     A->flist = nullptr;
     if (e == hipSuccess && A->nlinks == 1)
-        A->flist = (uint16_t *)scratch_get(scr, 44, size_t(A->nunits) * A->fl_stride * kPbLanes * 2, &e);
+        A->flist = (uint16_t *)scratch_get(scr, kScrPartFlist, size_t(A->nunits) * A->fl_stride * kPbLanes * 2, &e);
     return e;
 }
 

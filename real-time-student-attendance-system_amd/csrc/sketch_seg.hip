@@ -806,8 +806,8 @@ bool seg_use(const PartArgs &A, const SegOpts &so, uint32_t nslots, uint64_t n, 
     return n * 100 >= thr * nslots * (kHllRegs / 128);
 }
 
-// the segmented PFADD's scratch (context slots 32, 36-43 and 45; 33-35, the
-// run-table form's until round 8, are free)
+// the segmented PFADD's scratch (context slots kScrSeg*, ordered with K1's
+// through ske_ctx::xr; routing has slots of its own)
 hipError_t seg_scratch(const SegPlan &P, uint32_t sub, uint64_t n, Scratch *scr, SegArgs *S) {
     const uint64_t mg = std::min<uint64_t>(n, uint64_t(P.nsub) * sub);  // swipes of one window pass
     hipError_t e = hipSuccess;
@@ -815,24 +815,24 @@ hipError_t seg_scratch(const SegPlan &P, uint32_t sub, uint64_t n, Scratch *scr,
     const SegSlots L = seg_slots(P, sub, n);
     S->kstat = L.kstat;
     S->kmaxc = L.kmaxc;
-    S->r1 = (uint32_t *)scratch_get(scr, 32, size_t(L.r1_slots) * kSegChunk * 4, &e);
+    S->r1 = (uint32_t *)scratch_get(scr, kScrSegR1, size_t(L.r1_slots) * kSegChunk * 4, &e);
     if (e == hipSuccess)
-        S->fill = (uint32_t *)scratch_get(scr, 40, size_t(P.nsub) * (P.nb1 + 1) * kSegFillStride * 4, &e);
-    if (e == hipSuccess) S->ctab = (uint32_t *)scratch_get(scr, 41, size_t(P.nb1) * S->kmaxc * 4, &e);
+        S->fill = (uint32_t *)scratch_get(scr, kScrSegFill, size_t(P.nsub) * (P.nb1 + 1) * kSegFillStride * 4, &e);
+    if (e == hipSuccess) S->ctab = (uint32_t *)scratch_get(scr, kScrSegCtab, size_t(P.nb1) * S->kmaxc * 4, &e);
     if (e == hipSuccess)
-        S->r2 = (uint32_t *)scratch_get(scr, 36, size_t(L.rows) * kSegChunk * 4, &e);
+        S->r2 = (uint32_t *)scratch_get(scr, kScrSegR2, size_t(L.rows) * kSegChunk * 4, &e);
     if (e == hipSuccess)
-        S->o2 = (uint32_t *)scratch_get(scr, 37, size_t(L.rows) * ((1u << P.wlog) + 1) * 4, &e);
-    if (e == hipSuccess) S->cb = (uint32_t *)scratch_get(scr, 38, size_t(P.nsub) * (P.nb1 + 1) * 4, &e);
+        S->o2 = (uint32_t *)scratch_get(scr, kScrSegO2, size_t(L.rows) * ((1u << P.wlog) + 1) * 4, &e);
+    if (e == hipSuccess) S->cb = (uint32_t *)scratch_get(scr, kScrSegCb, size_t(P.nsub) * (P.nb1 + 1) * 4, &e);
     // the window pass's cut windows: a cut window has > slice records and
     // ceil(records / slice) < 2 records / slice slices, so 2 n / slice
     // copies, queue entries and cut windows always suffice
     const uint32_t ccap = uint32_t(2 * ((mg + seg_slice(P.klog) - 1) / seg_slice(P.klog)) + 2);
     const size_t wb = size_t(1) << (P.klog + kHllP);
-    if (e == hipSuccess) S->q = (uint32_t *)scratch_get(scr, 39, 64, &e);
-    if (e == hipSuccess) S->qitems = (uint4 *)scratch_get(scr, 42, size_t(ccap) * 16, &e);
-    if (e == hipSuccess) S->mlist = (uint4 *)scratch_get(scr, 43, size_t(ccap) * 16, &e);
-    if (e == hipSuccess) S->copies = (uint8_t *)scratch_get(scr, 45, size_t(ccap) * wb, &e);
+    if (e == hipSuccess) S->q = (uint32_t *)scratch_get(scr, kScrSegQ, 64, &e);
+    if (e == hipSuccess) S->qitems = (uint4 *)scratch_get(scr, kScrSegQitems, size_t(ccap) * 16, &e);
+    if (e == hipSuccess) S->mlist = (uint4 *)scratch_get(scr, kScrSegMlist, size_t(ccap) * 16, &e);
+    if (e == hipSuccess) S->copies = (uint8_t *)scratch_get(scr, kScrSegCopies, size_t(ccap) * wb, &e);
     S->ccap = ccap;
     S->nb1 = P.nb1;
     S->s1 = P.s1;

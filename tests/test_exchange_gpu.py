@@ -120,6 +120,59 @@ def test_route_cap_layout(engine, slack, world):
         assert np.isin(have, want).all()
 
 
+def test_route_beside_segmented_k1(orc, engine):
+    """Routing on one stream beside the partitioned K1 with the segmented
+    PFADD on another, as the pipelined exchange runs them at C3: four rounds
+    of a 300 000-swipe K1 (stream K) and a 300 000-id capacity routing
+    (stream R) with no host synchronisation between them.  Routing's scratch
+    (the histogram) and the segmented PFADD's (fill counts, chunk table) are
+    different slots of the context scratch, ordered apart (ScratchSlot,
+    csrc/sketch_internal.h), so both must come out exact: answers and
+    registers == the oracle over the four batches, every round's counts and
+    positions == the owners'.  (Coverage of the combination, not a race
+    detector.)"""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_seg_pfadd import _c3, _oracle
+    from rtsas_amd.distributed import KeyMap, SwipeExchange
+    from rtsas_amd.engine import DeviceBuffer
+    w, p = _c3(engine)  # 200 000 members, 370 keys, the partitioned K1
+    engine.set_option("hll_seg", 1)
+    world, n, rounds = 3, 300_000, 4
+    km = KeyMap([f"hll:unique:L{k:03d}:2025-01-01" for k in range(37)], world)
+    sinks = [km.slots_end(r) for r in range(world)]
+    ex = SwipeExchange(0, world, None, km, engine=engine, sink_slots=sinks, slack=0.2)
+    cap = ex.capacity(n)
+    rng = np.random.default_rng(11)
+    batches = [engine.swipe_batch(p, r * n, n) for r in range(rounds)]
+    outs = [DeviceBuffer(engine.ctx, n) for _ in range(rounds)]
+    gks = [rng.integers(-1, 40, n).astype(np.int32) for _ in range(rounds)]  # -1, 37..39: outside the universe
+    ids = [torch.from_numpy(rng.integers(48, 58, (n, 8), dtype=np.uint8)).cuda() for _ in range(rounds)]
+    gkd = [torch.from_numpy(g).cuda() for g in gks]
+    sk, sr = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    routed = []
+    try:
+        for r in range(rounds):
+            engine.set_stream(sk.cuda_stream)
+            engine.swipes_async(0, batches[r], outs[r])  # (enqueue only: ske_swipes would wait for stream K)
+            with torch.cuda.stream(sr):
+                routed.append(ex._route_cap_native(ids[r], gkd[r], cap))
+    finally:
+        engine.set_stream(None)
+    torch.cuda.synchronize()
+    engine.check_errors()
+    _, regs, answers = _oracle(orc, engine, w, p, batches)
+    for r in range(rounds):
+        assert np.array_equal(outs[r].to_host(np.uint8, n), answers[r]), f"round {r} answers"
+        known = (gks[r] >= 0) & (gks[r] < 37)
+        own = np.where(known, km.owner[np.where(known, gks[r], 0)], 0).astype(np.int64)
+        _, _, pos, counts = routed[r]
+        assert counts.cpu().numpy().tolist() == np.bincount(own, minlength=world).tolist(), f"round {r} counts"
+        assert ((pos.cpu().numpy()[:n].astype(np.int64) // cap) == own).all(), f"round {r} positions"
+    assert np.array_equal(engine.registers_all(w.n_keys), regs)
+
+
 @pytest.mark.parametrize("padded,base", [(True, 0), (False, 0), (True, 2)])
 def test_solo_exchange_identity_vs_oracle(orc, engine, padded, base):
     """World 1 without a process group: SwipeExchange.swipes_async is the
