@@ -27,8 +27,9 @@
  *   - a context is single-threaded and stream-ordered; every call returns
  *     after its work on the context stream completed, except ske_swipes_async.
  *   - filters are addressed by a caller-chosen id `fid` < SKE_MAX_FILTERS, HLL
- *     keys by a caller-chosen register-slab slot.  The facade maps Redis key
- *     names to fids / slots.
+ *     keys by a caller-chosen register-slab slot, Count-Min Sketch tables by a
+ *     caller-chosen `cid` < SKE_MAX_CMS.  The facade maps Redis key names to
+ *     fids / slots / cids.
  */
 #ifndef SKETCH_H
 #define SKETCH_H
@@ -54,12 +55,26 @@ extern "C" {
 #define SKE_EBADHLL -11      /* corrupted HLL string on import */
 #define SKE_ETOOLONG -12     /* item longer than the supported maximum */
 #define SKE_EBUSY -13        /* device buffers (scratch, HLL slab) pinned by a recorded graph */
+#define SKE_ECMSNOKEY -14    /* "CMS: key does not exist" */
+#define SKE_ECMSEXISTS -15   /* "CMS: key already exists" */
+#define SKE_ECMSWIDTH -16    /* "CMS: invalid width" */
+#define SKE_ECMSDEPTH -17    /* "CMS: invalid depth" */
+#define SKE_ECMSDIMS -18     /* "CMS: width/depth is not equal" */
+#define SKE_ECMSNEG -19      /* "CMS: Number cannot be negative" */
+#define SKE_ECMSOVERFLOW -20 /* "CMS: MERGE overflow" */
+#define SKE_ECMSERROR -21    /* "CMS: invalid overestimation value" (CMS.INITBYPROB error) */
+#define SKE_ECMSPROB -22     /* "CMS: invalid prob value" (CMS.INITBYPROB probability) */
+#define SKE_ECMSPARSE -23    /* "CMS: Cannot parse number" */
 
 #define SKE_MEM_HOST 0
 #define SKE_MEM_DEVICE 1
 
 #define SKE_MAX_FILTERS 4096
 #define SKE_MAX_LINKS 48
+#define SKE_MAX_CMS 4096
+#define SKE_CMS_MAX_DEPTH 64
+#define SKE_CMS_MAX_CELLS (1u << 28) /* width * depth stays below this */
+#define SKE_CMS_MAX_MERGE 64
 #define SKE_HLL_REGISTERS 16384
 #define SKE_HLL_DENSE_BYTES 12288
 
@@ -200,6 +215,66 @@ int ske_hll_merge_groups_dev(ske_ctx *ctx, const uint32_t *slots, const uint32_t
                              uint32_t ngroups, uint8_t *dst_dev);
 /* estimator only: PFCOUNT of raw register arrays already on the device */
 int ske_hll_count_raw_dev(ske_ctx *ctx, const uint8_t *regs_dev, uint32_t nkeys, uint64_t *out);
+
+/* ---- Count-Min Sketch (RedisBloom src/cms.c) ----
+ * A table of `depth` rows of `width` u32 counters (row-major) and a u64 count
+ * of all increments; the cell of an item in row i is
+ * MurmurHash2(item, len, seed = i) % width (the 32-bit MurmurHash2).  Tables
+ * are addressed by a caller-chosen cid < SKE_MAX_CMS; the context owns them.
+ * No reference counterpart in its Redis calls: the per-student counts of
+ * attendance_analysis.py:99-118 and :65-75 come from pandas over Cassandra
+ * rows; these entry points keep them beside the swipe path instead.
+ * Limits of this build: depth <= SKE_CMS_MAX_DEPTH, width * depth <
+ * SKE_CMS_MAX_CELLS, n < 2^32 - 1 items per call. */
+typedef struct {
+    uint64_t width;
+    uint64_t depth;
+    uint64_t count;
+} ske_cms_info_t;
+/* CMS.INITBYPROB's dimensions: width = ceil(2 / error), depth =
+ * ceil(log10f(prob) / log10f(0.5f)); both arguments in (0, 1), else
+ * SKE_ECMSERROR / SKE_ECMSPROB.  Host only, no context. */
+int ske_cms_dims_from_prob(double error, double prob, uint32_t *width, uint32_t *depth);
+/* CMS.INITBYDIM key width depth (a zeroed table).  SKE_ECMSEXISTS when cid is
+ * in use, SKE_ECMSWIDTH / SKE_ECMSDEPTH for a zero or out-of-limit dimension. */
+int ske_cms_init(ske_ctx *ctx, uint32_t cid, uint32_t width, uint32_t depth);
+int ske_cms_free(ske_ctx *ctx, uint32_t cid);
+/* CMS.INFO key */
+int ske_cms_info(ske_ctx *ctx, uint32_t cid, ske_cms_info_t *out);
+/* CMS.INCRBY key item increment [item increment ...]: every row's cell of
+ * item i += incr[i] (1 each when incr is NULL), a cell that would pass
+ * 0xffffffff stays there; count += incr[i].
+ *   reply != NULL: the sequential form -- items in order, reply[i] = the
+ *     minimum of item i's cells right after its update (repeats and
+ *     collisions inside the call show); one wavefront, not a throughput path;
+ *   reply == NULL: the bulk form -- order-free, every cell ends at
+ *     min(true sum, 2^32 - 1), the same table the sequential form leaves. */
+int ske_cms_incrby(ske_ctx *ctx, uint32_t cid, const uint8_t *bytes, const uint32_t *offs,
+                   uint64_t n, const uint32_t *incr_or_null, uint32_t *reply_or_null, int mem);
+/* The bulk form over fixed-width ids on the device (id i = the `width` bytes
+ * at ids + i * width), enqueue only and graph-capturable: the form that
+ * follows ske_swipes*_async on the same stream.  mask (may be NULL): only
+ * items with mask[i] == want (0 or 1) count -- K1's answer bytes read in
+ * place ("count this swipe's student if it was invalid", or valid). */
+int ske_cms_add_fixed_async(ske_ctx *ctx, uint32_t cid, const uint8_t *ids, uint32_t width,
+                            uint64_t n, const uint32_t *incr_or_null, const uint8_t *mask_or_null,
+                            int want);
+/* CMS.QUERY key item...: out[i] = the minimum of item i's cells */
+int ske_cms_query(ske_ctx *ctx, uint32_t cid, const uint8_t *bytes, const uint32_t *offs,
+                  uint64_t n, uint32_t *out, int mem);
+/* CMS.MERGE dst nsrc src... [WEIGHTS w...]: dst[cell] = sum of src_k[cell] *
+ * w_k (weights NULL: 1 each), count likewise; dst is overwritten and takes
+ * part only when listed as a source.  SKE_ECMSDIMS unless every table has
+ * dst's dimensions.  Sums are formed in signed 64-bit arithmetic; a cell
+ * outside [0, 2^32 - 1], a count outside [0, 2^64 - 1] or a 64-bit overflow
+ * on the way fails the call with SKE_ECMSOVERFLOW before dst is written.
+ * 1 <= nsrc <= SKE_CMS_MAX_MERGE. */
+int ske_cms_merge(ske_ctx *ctx, uint32_t dst, const uint32_t *srcs, const int64_t *weights_or_null,
+                  uint32_t nsrc);
+/* the whole table, row-major (cap_cells >= width * depth), and back: import
+ * overwrites cells and count (ncells must equal width * depth) */
+int ske_cms_export(ske_ctx *ctx, uint32_t cid, uint32_t *out, uint64_t cap_cells);
+int ske_cms_import(ske_ctx *ctx, uint32_t cid, const uint32_t *in, uint64_t ncells, uint64_t count);
 
 /* ---- the fused hot path (K1) ----
  * For every swipe i: v = BF.EXISTS fid id_i; if v: PFADD slot_i id_i.
@@ -375,7 +450,7 @@ int ske_ingest_swipes(ske_ctx *ctx, uint32_t fid, const uint8_t *msgs,
 /* ---- stream capture (HIP graphs) ----
  * Record the device work of the calls made between begin and end on the
  * context stream (only enqueue-only calls: ske_swipes_async,
- * ske_swipes_fixed_async) into an executable graph, uploaded to the device;
+ * ske_swipes_fixed_async, ske_cms_add_fixed_async) into an executable graph, uploaded to the device;
  * each ske_graph_launch replays it on the context stream.  A consumer that
  * processes a ring of fixed device batch slots replays one graph per turn of
  * the ring instead of one launch per batch (SURVEY.md §8a-1's processor loop at

@@ -7,15 +7,16 @@ attendance_processor.py:152), executed by hand-written gfx950 HIP kernels in
 """
 from . import exceptions
 from ._lib import Context, SketchLibError, load as load_library, LIB_PATH
-from .client import BloomCommands, Pipeline, Redis, SketchClient
+from .analysis import StudentCounts
+from .client import BloomCommands, CMSCommands, Pipeline, Redis, SketchClient
 from .config import AttendanceConfig
 from .encoding import encode, pack, pack_ints
 from .exceptions import DataError, RedisError, ResponseError
 from .processor import AttendanceProcessor, campus_rollup, lecture_rankings
 
 __all__ = [
-    "AttendanceConfig", "AttendanceProcessor", "BloomCommands", "Context", "DataError",
+    "AttendanceConfig", "AttendanceProcessor", "BloomCommands", "CMSCommands", "Context", "DataError",
     "LIB_PATH", "Pipeline", "Redis", "RedisError", "ResponseError", "SketchClient",
-    "SketchLibError", "campus_rollup", "encode", "exceptions", "lecture_rankings",
+    "SketchLibError", "StudentCounts", "campus_rollup", "encode", "exceptions", "lecture_rankings",
     "load_library", "pack", "pack_ints",
 ]

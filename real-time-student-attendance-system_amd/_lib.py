@@ -29,9 +29,21 @@ SKE_EBADEXP = -10
 SKE_EBADHLL = -11
 SKE_ETOOLONG = -12
 SKE_EBUSY = -13
+SKE_ECMSNOKEY = -14
+SKE_ECMSEXISTS = -15
+SKE_ECMSWIDTH = -16
+SKE_ECMSDEPTH = -17
+SKE_ECMSDIMS = -18
+SKE_ECMSNEG = -19
+SKE_ECMSOVERFLOW = -20
+SKE_ECMSERROR = -21
+SKE_ECMSPROB = -22
+SKE_ECMSPARSE = -23
 SKE_MEM_HOST = 0
 SKE_MEM_DEVICE = 1
 SKE_MAX_FILTERS = 4096
+SKE_MAX_CMS = 4096
+SKE_CMS_MAX_MERGE = 64
 HLL_REGISTERS = 16384
 HLL_DENSE_BYTES = 12288
 
@@ -54,6 +66,10 @@ class BfLink(C.Structure):
     _fields_ = [("entries", C.c_uint64), ("bytes", C.c_uint64), ("bits", C.c_uint64),
                 ("size", C.c_uint64), ("error", C.c_double), ("bpe", C.c_double),
                 ("hashes", C.c_int32), ("pad_", C.c_int32)]
+
+
+class CmsInfo(C.Structure):
+    _fields_ = [("width", C.c_uint64), ("depth", C.c_uint64), ("count", C.c_uint64)]
 
 
 class IngestCols(C.Structure):
@@ -114,6 +130,18 @@ SIGNATURES = {
     "ske_hll_slab": (C.c_int, [_CTX, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "ske_hll_merge_groups_dev": (C.c_int, [_CTX, _u32p, _u32p, C.c_uint32, _u8p]),
     "ske_hll_count_raw_dev": (C.c_int, [_CTX, _u8p, C.c_uint32, _u64p]),
+    "ske_cms_dims_from_prob": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint32)]),
+    "ske_cms_init": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "ske_cms_free": (C.c_int, [_CTX, C.c_uint32]),
+    "ske_cms_info": (C.c_int, [_CTX, C.c_uint32, C.POINTER(CmsInfo)]),
+    "ske_cms_incrby": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, C.c_uint64, _u32p, _u32p, C.c_int]),
+    "ske_cms_add_fixed_async": (C.c_int, [_CTX, C.c_uint32, _u8p, C.c_uint32, C.c_uint64, _u32p, _u8p,
+                                          C.c_int]),
+    "ske_cms_query": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, C.c_uint64, _u32p, C.c_int]),
+    "ske_cms_merge": (C.c_int, [_CTX, C.c_uint32, _u32p, _vp, C.c_uint32]),
+    "ske_cms_export": (C.c_int, [_CTX, C.c_uint32, _u32p, C.c_uint64]),
+    "ske_cms_import": (C.c_int, [_CTX, C.c_uint32, _u32p, C.c_uint64, C.c_uint64]),
     "ske_swipes": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p, C.c_int]),
     "ske_swipes_async": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p]),
     "ske_swipes_fixed": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, C.c_uint32, C.c_uint64, _u8p,

@@ -19,6 +19,10 @@ plus the north-star surface: ``bf().reserve/add/madd/exists/mexists/info``,
 ``pfmerge``, ``pipeline()`` and the batched ``swipes()`` (the fused K1 kernel:
 BF.EXISTS then valid-gated PFADD for a whole batch of events).
 
+Per-student counters (attendance_analysis.py:99-118, there pandas over
+Cassandra rows) are RedisBloom Count-Min Sketch keys: the six ``CMS.*``
+commands, ``cms()`` with redis-py's surface and the bulk ``cms_add_packed``.
+
 Semantics kept from Redis / RedisBloom / redis-py:
   * argument encoding as redis-py (``encoding.encode``);
   * ``BF.EXISTS``/``BF.MEXISTS`` on a missing key answer 0 (so the
@@ -37,13 +41,14 @@ from typing import Iterable, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (BfInfo, BfLink, Context, SketchLibError, SKE_MEM_DEVICE, SKE_MEM_HOST,
+from ._lib import (BfInfo, BfLink, CmsInfo, Context, SketchLibError, SKE_MEM_DEVICE, SKE_MEM_HOST,
                    HLL_DENSE_BYTES, HLL_REGISTERS)
 from . import formats
 from .encoding import encode, pack
 from .exceptions import DataError, ResponseError, WRONGTYPE
 
 BF_TYPE_NAME = "MBbloom--"  # RedisBloom's module type name (TYPE reply)
+CMS_TYPE_NAME = "CMSk-TYPE"  # RedisBloom's Count-Min Sketch type name (TYPE reply)
 _DEFAULT_ERROR = 0.01       # rebloom.c BFDefaultErrorRate
 _DEFAULT_CAPACITY = 100     # rebloom.c BFDefaultInitCapacity
 _DEFAULT_EXPANSION = 2      # rebloom.c BFDefaultExpansion
@@ -58,14 +63,17 @@ def _err(e: SketchLibError) -> ResponseError:
 
 
 class KeySpace:
-    """Key name -> device object (Bloom fid or HLL register-slab slot)."""
+    """Key name -> device object (Bloom fid, HLL register-slab slot or
+    Count-Min Sketch cid)."""
 
     def __init__(self, ctx: Context):
         self.ctx = ctx
         self.kind: dict[bytes, str] = {}
         self.fid: dict[bytes, int] = {}
         self.slot: dict[bytes, int] = {}
+        self.cid: dict[bytes, int] = {}
         self._free_fids = list(range(_lib.SKE_MAX_FILTERS - 1, -1, -1))
+        self._free_cids = list(range(_lib.SKE_MAX_CMS - 1, -1, -1))
         self._free_slots: list[int] = []
         self._next_slot = 0
         self._slot_key: dict[int, bytes] = {}
@@ -100,7 +108,7 @@ class KeySpace:
 
     def expect(self, key: bytes, kind: str) -> bool:
         """True if the key exists with this kind, False if missing; raises
-        WRONGTYPE if it holds the other kind."""
+        WRONGTYPE if it holds another kind."""
         k = self.kind.get(key)
         if k is None:
             return False
@@ -115,6 +123,14 @@ class KeySpace:
         self.kind[key] = "bf"
         self.fid[key] = f
         return f
+
+    def new_cid(self, key: bytes) -> int:
+        if not self._free_cids:
+            raise ResponseError("ERR too many Count-Min Sketch keys on this device")
+        t = self._free_cids.pop()
+        self.kind[key] = "cms"
+        self.cid[key] = t
+        return t
 
     def new_slot(self, key: bytes) -> int:
         if self._free_slots:
@@ -162,6 +178,10 @@ class KeySpace:
             f = self.fid.pop(key)
             self.ctx.call("ske_bf_free", f)
             self._free_fids.append(f)
+        elif k == "cms":
+            t = self.cid.pop(key)
+            self.ctx.call("ske_cms_free", t)
+            self._free_cids.append(t)
         elif k == "hll":
             s = self.slot.pop(key)
             self._slot_key.pop(s, None)
@@ -298,7 +318,7 @@ class SketchClient:
         pat = encode(match if match is not None else "*")
         every = pat == b"*"  # SCAN's own bypass (the glob rule alone would skip an empty key name)
         for k in sorted(self.keys.kind):
-            if (every or redis_glob(pat, k)) and (_type is None or self.keys.kind[k] == {"string": "hll", "MBbloom--": "bf"}.get(
+            if (every or redis_glob(pat, k)) and (_type is None or self.keys.kind[k] == {"string": "hll", "MBbloom--": "bf", "CMSk-TYPE": "cms"}.get(
                     _type, _type)):
                 yield k.decode() if self.decode_responses else k
 
@@ -310,7 +330,7 @@ class SketchClient:
 
     def type(self, name):
         k = self.keys.type_of(encode(name))
-        return self._s({"bf": BF_TYPE_NAME, "hll": "string", None: "none"}[k])
+        return self._s({"bf": BF_TYPE_NAME, "hll": "string", "cms": CMS_TYPE_NAME, None: "none"}[k])
 
     def flushall(self, *_a, **_k) -> bool:
         for key in list(self.keys.kind):
@@ -492,6 +512,160 @@ class SketchClient:
 
     def bf(self) -> "BloomCommands":
         return BloomCommands(self)
+
+    # ------------------------------------------------------------ Count-Min Sketch
+    # RedisBloom src/rm_cms.c / src/cms.c, restated from memory (parity with a
+    # live RedisBloom is unpinned, DESIGN.md "Count-Min Sketch").  The error
+    # texts come from ske_strerror.
+    @staticmethod
+    def _cms_err(code: int) -> ResponseError:
+        return ResponseError(_lib.strerror(code))
+
+    @staticmethod
+    def _cms_int(v, code: int) -> int:
+        """A command argument as RedisModule_StringToLongLong reads it."""
+        try:
+            if isinstance(v, (bytes, bytearray, memoryview)):
+                v = bytes(v).decode()
+            if isinstance(v, float) and v != int(v):
+                raise ValueError
+            return int(v)
+        except (TypeError, ValueError, UnicodeDecodeError):
+            raise ResponseError(_lib.strerror(code))
+
+    def _cms_cid(self, key: bytes) -> int:
+        if not self.keys.expect(key, "cms"):
+            raise self._cms_err(_lib.SKE_ECMSNOKEY)
+        return self.keys.cid[key]
+
+    def cms_initbydim(self, key, width, depth):
+        key = encode(key)
+        w = self._cms_int(width, _lib.SKE_ECMSWIDTH)
+        if not 1 <= w <= 0xFFFFFFFF:
+            raise self._cms_err(_lib.SKE_ECMSWIDTH)
+        d = self._cms_int(depth, _lib.SKE_ECMSDEPTH)
+        if not 1 <= d <= 0xFFFFFFFF:
+            raise self._cms_err(_lib.SKE_ECMSDEPTH)
+        if key in self.keys.kind:  # CMS.INITBY* refuse a key of any type
+            raise self._cms_err(_lib.SKE_ECMSEXISTS)
+        t = self.keys.new_cid(key)
+        try:
+            self.ctx.call("ske_cms_init", t, w, d)
+        except SketchLibError as e:
+            self.keys.kind.pop(key, None)
+            self.keys.cid.pop(key, None)
+            self.keys._free_cids.append(t)
+            raise _err(e)
+        return self._ok()
+
+    def cms_initbyprob(self, key, error, probability):
+        try:
+            err = float(error)
+        except (TypeError, ValueError):
+            raise self._cms_err(_lib.SKE_ECMSERROR)
+        try:
+            prob = float(probability)
+        except (TypeError, ValueError):
+            raise self._cms_err(_lib.SKE_ECMSPROB)
+        w, d = C.c_uint32(), C.c_uint32()
+        rc = _lib.load().ske_cms_dims_from_prob(err, prob, C.byref(w), C.byref(d))
+        if rc:
+            raise self._cms_err(rc)
+        return self.cms_initbydim(key, w.value, d.value)
+
+    def cms_add_packed(self, key, buf: np.ndarray, offs: np.ndarray, incr=None, mask=None,
+                       want: int = 1) -> None:
+        """The bulk, order-free CMS.INCRBY over a packed batch (no replies):
+        item i counts ``incr[i]`` (1 when ``incr`` is None); with ``mask`` only
+        the items with ``mask[i] == want``."""
+        t = self._cms_cid(encode(key))
+        n = len(offs) - 1
+        if n <= 0:
+            return
+        inc = None if incr is None else np.ascontiguousarray(incr, dtype=np.uint32)
+        if inc is not None and inc.shape != (n,):
+            raise ValueError("one increment per item")
+        if mask is not None:
+            m = np.asarray(mask)
+            if m.shape != (n,):
+                raise ValueError("one mask byte per item")
+            if want not in (0, 1):
+                raise ValueError("want is 0 or 1")
+            inc = np.where(m == want, np.uint32(1) if inc is None else inc, np.uint32(0)).astype(np.uint32)
+        self.ctx.call("ske_cms_incrby", t, _ptr(np.ascontiguousarray(buf, np.uint8)),
+                      _ptr(np.ascontiguousarray(offs, np.uint32)), n, _ptr(inc), None, SKE_MEM_HOST)
+
+    def cms_incrby(self, key, items: Sequence, increments: Sequence) -> list[int]:
+        """CMS.INCRBY's reply list: per item the minimum of its cells right
+        after its own update, items taken in order."""
+        key = encode(key)
+        if len(items) != len(increments) or not items:
+            raise ResponseError("ERR wrong number of arguments for 'cms.incrby' command")
+        t = self._cms_cid(key)
+        inc = []
+        for v in increments:
+            x = self._cms_int(v, _lib.SKE_ECMSPARSE)
+            if x < 0:
+                raise self._cms_err(_lib.SKE_ECMSNEG)
+            if x > 0xFFFFFFFF:  # a counter is 32 bits wide (DESIGN.md: deviation)
+                raise self._cms_err(_lib.SKE_ECMSPARSE)
+            inc.append(x)
+        buf, offs = pack(items)
+        inc = np.asarray(inc, dtype=np.uint32)
+        out = np.zeros(len(items), np.uint32)
+        self.ctx.call("ske_cms_incrby", t, _ptr(buf), _ptr(offs), len(items), _ptr(inc), _ptr(out),
+                      SKE_MEM_HOST)
+        return [int(x) for x in out]
+
+    def cms_query_packed(self, key, buf: np.ndarray, offs: np.ndarray) -> np.ndarray:
+        t = self._cms_cid(encode(key))
+        n = len(offs) - 1
+        out = np.zeros(max(n, 0), np.uint32)
+        if n > 0:
+            self.ctx.call("ske_cms_query", t, _ptr(np.ascontiguousarray(buf, np.uint8)),
+                          _ptr(np.ascontiguousarray(offs, np.uint32)), n, _ptr(out), SKE_MEM_HOST)
+        return out
+
+    def cms_query(self, key, *items) -> list[int]:
+        buf, offs = pack(items)
+        return [int(x) for x in self.cms_query_packed(key, buf, offs)]
+
+    def cms_merge(self, dest, num_keys, src_keys: Sequence, weights: Sequence = ()):
+        d = self._cms_cid(encode(dest))
+        nk = self._cms_int(num_keys, _lib.SKE_ECMSPARSE)
+        if nk < 1 or nk != len(src_keys) or (len(weights) and len(weights) != nk):
+            raise ResponseError("ERR wrong number of arguments for 'cms.merge' command")
+        if nk > _lib.SKE_CMS_MAX_MERGE:
+            raise ResponseError(f"ERR at most {_lib.SKE_CMS_MAX_MERGE} source keys")
+        srcs = np.asarray([self._cms_cid(encode(k)) for k in src_keys], dtype=np.uint32)
+        w = None
+        if len(weights):
+            ws = [self._cms_int(x, _lib.SKE_ECMSPARSE) for x in weights]
+            if any(not -2 ** 63 <= x < 2 ** 63 for x in ws):
+                raise self._cms_err(_lib.SKE_ECMSPARSE)
+            w = np.asarray(ws, dtype=np.int64)
+        try:
+            self.ctx.call("ske_cms_merge", d, _ptr(srcs), _ptr(w), nk)
+        except SketchLibError as e:
+            raise _err(e)
+        return self._ok()
+
+    def cms_info(self, key) -> dict:
+        t = self._cms_cid(encode(key))
+        info = CmsInfo()
+        self.ctx.call("ske_cms_info", t, C.byref(info))
+        return {"width": info.width, "depth": info.depth, "count": info.count}
+
+    def cms_table(self, key) -> tuple[np.ndarray, int]:
+        """The whole table, [depth, width] u32, and its count."""
+        t = self._cms_cid(encode(key))
+        i = self.cms_info(key)
+        out = np.zeros((i["depth"], i["width"]), np.uint32)
+        self.ctx.call("ske_cms_export", t, _ptr(out), out.size)
+        return out, i["count"]
+
+    def cms(self) -> "CMSCommands":
+        return CMSCommands(self)
 
     # ------------------------------------------------------------ HLL
     def _hll_slots_for_add(self, keys: Sequence[bytes]):
@@ -910,6 +1084,9 @@ class SketchClient:
             if len(a) < lo or (hi is not None and len(a) > hi):
                 raise ResponseError(f"ERR wrong number of arguments for '{name.lower()}' command")
 
+        def arity_error():
+            raise ResponseError(f"ERR wrong number of arguments for '{name.lower()}' command")
+
         if cmd == "BF.RESERVE":
             need(3)
             exp, nonscaling = None, False
@@ -957,6 +1134,41 @@ class SketchClient:
             need(1, 1)
             k = encode(a[0])
             return self.bf_info(k)["Number of items inserted"] if self.keys.expect(k, "bf") else 0
+        if cmd == "CMS.INITBYDIM":
+            need(3, 3)
+            return self.cms_initbydim(a[0], a[1], a[2])
+        if cmd == "CMS.INITBYPROB":
+            need(3, 3)
+            return self.cms_initbyprob(a[0], a[1], a[2])
+        if cmd == "CMS.INCRBY":
+            need(3)
+            if len(a) % 2 == 0:
+                arity_error()
+            return self.cms_incrby(a[0], a[1::2], a[2::2])
+        if cmd == "CMS.QUERY":
+            need(2)
+            return self.cms_query(a[0], *a[1:])
+        if cmd == "CMS.MERGE":
+            need(3)
+            nk = self._cms_int(a[1], _lib.SKE_ECMSPARSE)
+            rest = list(a[2:])
+            if nk < 1 or len(rest) < nk:
+                arity_error()
+            srcs, rest = rest[:nk], rest[nk:]
+            weights = []
+            if rest:
+                opt = rest[0].decode() if isinstance(rest[0], bytes) else str(rest[0])
+                if opt.upper() != "WEIGHTS" or len(rest) != nk + 1:
+                    arity_error()
+                weights = rest[1:]
+            return self.cms_merge(a[0], nk, srcs, weights)
+        if cmd == "CMS.INFO":
+            need(1, 1)
+            info = self.cms_info(a[0])
+            flat = []
+            for k, v in info.items():
+                flat += [self._s(k), v]
+            return flat
         if cmd == "PFADD":
             need(1)
             return self.pfadd(*a)
@@ -970,7 +1182,7 @@ class SketchClient:
         if cmd == "GET":
             need(1, 1)
             k = encode(a[0])
-            if self.keys.type_of(k) == "bf":
+            if self.keys.type_of(k) in ("bf", "cms"):
                 raise ResponseError(WRONGTYPE)
             return self.dump_hll(k)
         if cmd == "SET":
@@ -1029,6 +1241,49 @@ class BloomCommands:
 
     def card(self, key):
         return self.client.execute_command("BF.CARD", key)
+
+
+class CMSCommands:
+    """``client.cms()`` surface of redis-py (redis.commands.bf.CMSCommands)."""
+
+    def __init__(self, client: SketchClient):
+        self.client = client
+
+    def initbydim(self, key, width, depth):
+        self.client.execute_command("CMS.INITBYDIM", key, width, depth)
+        return True
+
+    def initbyprob(self, key, error, probability):
+        self.client.execute_command("CMS.INITBYPROB", key, error, probability)
+        return True
+
+    def incrby(self, key, items, increments):
+        return self.client.cms_incrby(key, list(items), list(increments))
+
+    def query(self, key, *items):
+        return self.client.execute_command("CMS.QUERY", key, *items)
+
+    def merge(self, destKey, numKeys, srcKeys, weights=[]):
+        self.client.cms_merge(destKey, numKeys, list(srcKeys), list(weights))
+        return True
+
+    def info(self, key):
+        return CMSInfo(self.client.cms_info(key))
+
+
+class CMSInfo:
+    """redis.commands.bf.info.CMSInfo attribute names."""
+
+    def __init__(self, d: dict):
+        self.width = d["width"]
+        self.depth = d["depth"]
+        self.count = d["count"]
+
+    def get(self, item):
+        return getattr(self, item)
+
+    def __getitem__(self, item):
+        return getattr(self, item)
 
 
 class BFInfo:

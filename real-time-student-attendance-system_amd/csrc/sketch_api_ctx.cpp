@@ -1,7 +1,8 @@
 // sketch_api_ctx.cpp -- libsketch C-ABI (include/sketch.h): the context's
 // lifecycle, options, the sticky error word, streams, host -> device staging,
 // pass timing, the scratch-use ordering and graph capture.  The other
-// subsystems are sketch_api_{bloom,hll,swipes,ingest}.cpp (map: sketch_ctx.h).
+// subsystems are sketch_api_{bloom,hll,swipes,ingest,cms}.cpp (map: sketch_ctx.h).
+#include <stdlib.h>
 #include <string.h>
 
 #include "sketch_ctx.h"
@@ -280,6 +281,17 @@ const char *ske_strerror(int code) {
     case SKE_EBADHLL: return "INVALIDOBJ Corrupted HLL object detected";
     case SKE_ETOOLONG: return "ERR item too long";
     case SKE_EBUSY: return "ERR device buffers in use by a recorded graph";
+    // RedisBloom's Count-Min Sketch texts (src/rm_cms.c)
+    case SKE_ECMSNOKEY: return "CMS: key does not exist";
+    case SKE_ECMSEXISTS: return "CMS: key already exists";
+    case SKE_ECMSWIDTH: return "CMS: invalid width";
+    case SKE_ECMSDEPTH: return "CMS: invalid depth";
+    case SKE_ECMSDIMS: return "CMS: width/depth is not equal";
+    case SKE_ECMSNEG: return "CMS: Number cannot be negative";
+    case SKE_ECMSOVERFLOW: return "CMS: MERGE overflow";
+    case SKE_ECMSERROR: return "CMS: invalid overestimation value";
+    case SKE_ECMSPROB: return "CMS: invalid prob value";
+    case SKE_ECMSPARSE: return "CMS: Cannot parse number";
     default: return "ERR unknown";
     }
 }
@@ -313,6 +325,10 @@ int ske_open(int device, ske_ctx **out) {
     }
     c->lds_ok = lds_bloom_setup() == hipSuccess;
     c->k1_ok = c->lds_ok && k1_lds_setup() == hipSuccess;
+    if (const char *v = getenv("SKE_CMS_LDS_CELLS")) {
+        const unsigned long long cells = strtoull(v, nullptr, 10);
+        if (cells < c->cms_lds_cells) c->cms_lds_cells = uint32_t(cells);
+    }
     if (hipMalloc(&c->zero16, 64) != hipSuccess || hipMemset(c->zero16, 0, 64) != hipSuccess) {
         ske_close(c);
         return SKE_ENOMEM;
@@ -326,6 +342,7 @@ int ske_close(ske_ctx *c) {
     (void)hipSetDevice(c->device);
     if (c->st) (void)hipStreamSynchronize(c->st);
     for (auto &F : c->filters) free_filter(F);
+    for (auto &T : c->cms) free_cms(T);
     if (c->regs) (void)hipFree(c->regs);
     if (c->tau) (void)hipFree(c->tau);
     if (c->sig) (void)hipFree(c->sig);

@@ -97,6 +97,96 @@ SKE_HD uint64_t murmur_short(uint64_t w, uint32_t len, uint64_t seed) {
     return mm_final(h);
 }
 
+// ---------------------------------------------------------------------------
+// MurmurHash2, the 32-bit form (RedisBloom deps/murmur2/MurmurHash2.c
+// MurmurHash2): the Count-Min Sketch's row hash, cell of row i =
+// MurmurHash2(item, len, seed = i) % width (src/cms.c).  Little-endian 4-byte
+// blocks, a tail of 3 / 2 / 1 bytes, then the final mix.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kMurmur2M = 0x5bd1e995u;
+
+SKE_HD uint32_t mm2_block(uint32_t h, uint32_t k) {
+    k *= kMurmur2M;
+    k ^= k >> 24;
+    k *= kMurmur2M;
+    h *= kMurmur2M;
+    h ^= k;
+    return h;
+}
+// t: the rem (1..3) tail bytes, little-endian, zero padded
+SKE_HD uint32_t mm2_tail(uint32_t h, uint32_t t) {
+    h ^= t;
+    h *= kMurmur2M;
+    return h;
+}
+SKE_HD uint32_t mm2_final(uint32_t h) {
+    h ^= h >> 13;
+    h *= kMurmur2M;
+    h ^= h >> 15;
+    return h;
+}
+
+// the routine itself over any byte string (byte loads only: no alignment and
+// no readable byte past the item is assumed)
+SKE_HD uint32_t murmur2_32(const uint8_t *p, uint32_t len, uint32_t seed) {
+    uint32_t h = seed ^ len;
+    const uint32_t nblk = len >> 2, rem = len & 3;
+    for (uint32_t j = 0; j < nblk; j++, p += 4)
+        h = mm2_block(h, uint32_t(p[0]) | uint32_t(p[1]) << 8 | uint32_t(p[2]) << 16 | uint32_t(p[3]) << 24);
+    if (rem) {
+        uint32_t t = p[0];
+        if (rem >= 2) t |= uint32_t(p[1]) << 8;
+        if (rem == 3) t |= uint32_t(p[2]) << 16;
+        h = mm2_tail(h, t);
+    }
+    return mm2_final(h);
+}
+
+// The same hash of an item of at most 16 bytes held as two little-endian
+// 64-bit words, zero padded (Item::w0 / w1): no memory access per row.
+SKE_HD uint32_t murmur2_32_words(uint64_t w0, uint64_t w1, uint32_t len, uint32_t seed) {
+    uint32_t h = seed ^ len;
+    const uint32_t nblk = len >> 2;
+    if (nblk >= 1) h = mm2_block(h, uint32_t(w0));
+    if (nblk >= 2) h = mm2_block(h, uint32_t(w0 >> 32));
+    if (nblk >= 3) h = mm2_block(h, uint32_t(w1));
+    if (nblk >= 4) h = mm2_block(h, uint32_t(w1 >> 32));
+    if (len & 3) {
+        // the padding above the tail bytes is zero, so the block that holds
+        // them is the tail value
+        const uint64_t w = nblk >= 2 ? w1 : w0;
+        h = mm2_tail(h, uint32_t(nblk & 1 ? w >> 32 : w));
+    }
+    return mm2_final(h);
+}
+
+// Exact n mod d for 32-bit n and a runtime divisor 1 <= d < 2^32 (the same
+// Granlund-Montgomery form as Divisor below, in 32 bits: l = ceil(log2 d),
+// m = floor(2^32 (2^l - d) / d) + 1, t = mulhi(m, n),
+// q = (t + ((n - t) >> min(l, 1))) >> max(l - 1, 0)).
+struct Div32 {
+    uint32_t d, m, sh1, sh2;
+};
+SKE_HD uint32_t fastmod32(uint32_t n, const Div32 &D) {
+#ifdef __HIP_DEVICE_COMPILE__
+    const uint32_t t = __umulhi(D.m, n);
+#else
+    const uint32_t t = uint32_t(uint64_t(D.m) * n >> 32);
+#endif
+    const uint32_t q = (t + ((n - t) >> D.sh1)) >> D.sh2;
+    return n - q * D.d;
+}
+inline Div32 make_div32(uint32_t d) {
+    Div32 D{};
+    D.d = d;
+    uint32_t l = 0;
+    while (l < 32 && (uint64_t(1) << l) < d) l++;
+    D.m = uint32_t(((uint64_t(1) << 32) * ((uint64_t(1) << l) - d)) / d + 1);
+    D.sh1 = l < 1 ? l : 1;
+    D.sh2 = l > 1 ? l - 1 : 0;
+    return D;
+}
+
 // hllPatLen(): index = low 14 bits, count = 1 + trailing zeros of
 // (hash >> 14) | 1<<50, in [1, 51].
 SKE_HD void hll_patlen(uint64_t hash, uint32_t &idx, uint32_t &rank) {

@@ -8,6 +8,7 @@
 //   sketch_api_hll.cpp     the register slab, PFADD, PFCOUNT, PFMERGE, export / import
 //   sketch_api_swipes.cpp  K1: variant choice, launch_k1, ske_swipes*, ske_route_*
 //   sketch_api_ingest.cpp  ingest, the key table, the generator
+//   sketch_api_cms.cpp     Count-Min Sketch tables: init, add, query, merge, export / import
 // A helper used by one unit is static there; what crosses units is declared here.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -44,6 +45,14 @@ struct Filter {
     bool nonscaling = false;
 };
 
+// one Count-Min Sketch table (cells == nullptr: the cid is free)
+struct Cms {
+    uint32_t *cells = nullptr;            // device: depth rows of width counters, then
+    unsigned long long *count = nullptr;  //   the count, in the same allocation
+    uint32_t width = 0, depth = 0;
+    Div32 div{};
+};
+
 struct Staged {
     const uint8_t *bytes = nullptr;
     const uint32_t *offs = nullptr;
@@ -66,6 +75,11 @@ struct ske_ctx {
     hipStream_t own = nullptr;
     hipStream_t st = nullptr;
     std::vector<ske::Filter> filters;
+    std::vector<ske::Cms> cms;  // by cid (sized on first use)
+    bool cms_lds_ready = false;  // cms_setup() done (first ske_cms_init; a failure fails that call)
+    // tables up to this many cells take the LDS form (the environment variable
+    // SKE_CMS_LDS_CELLS, read by ske_open, lowers it for A/B timing; 0: never)
+    uint32_t cms_lds_cells = ske::kCmsLdsCells;
     uint8_t *regs = nullptr;  // nslots * 16384
     uint32_t nslots = 0;
     double *tau = nullptr, *sig = nullptr;  // device estimator tables (lazy)
@@ -212,6 +226,9 @@ int check_call_err(ske_ctx *c);
 void free_filter(Filter &F);
 // the kernel view of F's chain (cached; the empty chain for a missing key)
 const ChainDev &chain_of(Filter *F);
+
+// ---- sketch_api_cms.cpp
+void free_cms(Cms &T);
 
 // ---- sketch_api_swipes.cpp
 bool use_lds(const ske_ctx *c, const ChainDev &ch);

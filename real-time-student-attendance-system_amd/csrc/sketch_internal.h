@@ -182,6 +182,42 @@ hipError_t launch_swipes_part(const ChainDev &ch, const PartBatch *bt, uint32_t 
                               void *hook_user = nullptr);
 
 
+// sketch_cms.hip -- Count-Min Sketch (RedisBloom src/cms.c): bulk add in two
+// forms, the sequential add with replies, query, weighted merge
+constexpr uint32_t kCmsLdsMaxBytes = 152 * 1024;         // the LDS form's private table (160 KiB per CU)
+constexpr uint32_t kCmsLdsCells = kCmsLdsMaxBytes / 4;   // tables up to this many cells take the LDS form
+constexpr int kCmsMaxMerge = 64;
+struct CmsTable {
+    uint32_t *cells;            // depth rows of width counters
+    unsigned long long *count;  // sum of all increments
+    Div32 div;                  // of width
+    uint32_t depth, ncells;
+};
+struct CmsItems {
+    const uint8_t *bytes;
+    const uint32_t *offs;  // nullptr: fixed-width ids (fixed_w bytes each)
+    uint32_t fixed_w;
+    uint32_t n;
+    const uint32_t *incr;  // nullptr: 1 each
+    const uint8_t *mask;   // nullptr: every item counts; else those with mask[i] == want
+    uint32_t want;
+};
+struct CmsMergeArgs {
+    const uint32_t *src[kCmsMaxMerge];
+    long long w[kCmsMaxMerge];
+    uint32_t nsrc, ncells;
+    uint32_t *dst;
+    unsigned int *flag;  // set when a cell leaves [0, 2^32 - 1] (or the 64-bit sum overflows)
+};
+hipError_t cms_setup();
+// order-free add; lds: each workgroup sums into a private LDS table first (T.ncells <= kCmsLdsCells)
+hipError_t launch_cms_add(const CmsTable &T, const CmsItems &I, bool lds, int cus, hipStream_t st);
+// items in order by one wavefront, reply[i] = min of item i's cells after its update
+hipError_t launch_cms_seq(const CmsTable &T, const CmsItems &I, uint32_t *reply, hipStream_t st);
+hipError_t launch_cms_query(const CmsTable &T, const CmsItems &I, uint32_t *out, int cus, hipStream_t st);
+// write == false: only the range check into M.flag; true: dst = the weighted sums
+hipError_t launch_cms_merge(const CmsMergeArgs &M, bool write, int cus, hipStream_t st);
+
 // sketch_order.hip -- order-exact paths (replies that depend on item order)
 struct Scratch;  // growable device scratch, owned by the context
 constexpr int kScratchSlots = 48;
@@ -264,6 +300,9 @@ enum StageSlot : int {
     kStgList,      // a slot list (PFCOUNT / PFMERGE) or key hashes (ske_keytab_insert)
     kStgList2,     // group offsets (PFCOUNT) or key slots (ske_keytab_insert)
     kStgCheck,     // the device slot-range check word (check_slots_dev)
+    kStgCmsIncr,   // ske_cms_incrby: an increment per item
+    kStgCmsReply,  // ske_cms_incrby / ske_cms_query: a u32 reply per item on its way to the host
+    kStgCmsFlag,   // ske_cms_merge: the overflow word of the check pass, then the sources' counts
     kStageSlotCount
 };
 

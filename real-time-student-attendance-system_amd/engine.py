@@ -13,7 +13,7 @@ import gc
 
 import numpy as np
 
-from ._lib import Context, GenParams, SKE_MEM_DEVICE
+from ._lib import CmsInfo, Context, GenParams, SKE_MEM_DEVICE
 from . import synthetic
 
 PASS_KINDS = 9  # SKE_PASS_KINDS (include/sketch.h)
@@ -261,6 +261,47 @@ class SketchEngine:
 
     def check_errors(self):
         self.ctx.call("ske_check_errors")
+
+    # ---- Count-Min Sketch (per-student counters beside the swipe path)
+    def cms_init(self, cid: int, width: int, depth: int):
+        self.ctx.call("ske_cms_init", int(cid), int(width), int(depth))
+
+    def cms_add(self, cid: int, b: DeviceBatch, mask: DeviceBuffer | None = None, want: int = 1,
+                incr: DeviceBuffer | None = None):
+        """The bulk, order-free add of a resident batch: item i counts
+        ``incr[i]`` (u32; 1 each without ``incr``), with ``mask`` only the
+        items whose mask byte equals ``want`` -- K1's answers read in place.
+        A fixed-width batch is only enqueued (ske_cms_add_fixed_async, after
+        swipes_fixed_async on the same stream, capturable; ``sync()`` waits);
+        a batch of bytes + offsets goes through ske_cms_incrby, which takes
+        no mask and returns when done."""
+        if b.width > 0:
+            self.ctx.call("ske_cms_add_fixed_async", int(cid), C.c_void_p(b.bytes.ptr), b.width, b.n,
+                          C.c_void_p(incr.ptr) if incr else None, C.c_void_p(mask.ptr) if mask else None,
+                          int(want))
+            return
+        if mask is not None:
+            raise ValueError("a masked add needs a fixed-width batch")
+        self.ctx.call("ske_cms_incrby", int(cid), C.c_void_p(b.bytes.ptr), C.c_void_p(b.offs.ptr), b.n,
+                      C.c_void_p(incr.ptr) if incr else None, None, SKE_MEM_DEVICE)
+
+    def cms_query(self, cid: int, b: DeviceBatch) -> np.ndarray:
+        """The estimate (minimum over the rows) of every item of the batch."""
+        out = DeviceBuffer(self.ctx, b.n * 4)
+        try:
+            self.ctx.call("ske_cms_query", int(cid), C.c_void_p(b.bytes.ptr), C.c_void_p(b.offs.ptr), b.n,
+                          C.c_void_p(out.ptr), SKE_MEM_DEVICE)
+            return out.to_host(np.uint32, b.n)
+        finally:
+            out.free()
+
+    def cms_table(self, cid: int) -> tuple[np.ndarray, int]:
+        """The whole table, [depth, width] u32, and its count."""
+        info = CmsInfo()
+        self.ctx.call("ske_cms_info", int(cid), C.byref(info))
+        out = np.zeros((info.depth, info.width), np.uint32)
+        self.ctx.call("ske_cms_export", int(cid), out.ctypes.data_as(C.c_void_p), out.size)
+        return out, int(info.count)
 
     # ---- HIP graphs: record enqueue-only calls once, replay many times
     def capture(self, fn) -> "Graph":
