@@ -6,7 +6,7 @@
  * this path through a redis-py client object (attendance_processor.py:37-41,
  * data_generator.py:45-49).  Each entry point below replaces one family of the
  * RESP round trips that client makes; the Python facade
- * (real-time-student-attendance-system_amd/client.py) keeps the redis-py call
+ * (real-time-student-attendance-system_amd/client.py, client_*.py) keeps the redis-py call
  * surface and binds these symbols through ctypes (INTEGRATION.md shows the
  * binding).
  *

@@ -209,6 +209,11 @@ def load() -> C.CDLL:
     return lib
 
 
+def ptr(a):
+    """A numpy array (or None) as the void pointer argument of a call."""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
 def strerror(code: int) -> str:
     return load().ske_strerror(code).decode()
 

@@ -75,7 +75,7 @@ class StudentCounts:
         else:
             d_valid.from_host(np.zeros(n, np.uint8))  # BF.EXISTS of a missing key answers 0
         for key, want in ((self.attended_key, 1), (self.invalid_key, 0)):
-            cl.ctx.call("ske_cms_add_fixed_async", cl._cms_cid(encode(key)), C.c_void_p(d_ids.ptr), width, n,
+            cl.ctx.call("ske_cms_add_fixed_async", cl.cms_cid(key), C.c_void_p(d_ids.ptr), width, n,
                         None, C.c_void_p(d_valid.ptr), want)
         cl.ctx.call("ske_sync")
         return d_valid.to_host(np.uint8, n).astype(bool)

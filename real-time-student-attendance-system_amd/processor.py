@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import json
 import logging
-from datetime import datetime, timezone
+from datetime import datetime
 from typing import Iterable, Sequence
 
 import numpy as np
@@ -23,6 +23,7 @@ from .client import SketchClient
 from .config import AttendanceConfig
 from .encoding import encode
 from .exceptions import ResponseError
+from .keyspace import day_key
 
 logger = logging.getLogger(__name__)
 
@@ -58,11 +59,8 @@ class AttendanceProcessor:
 
     def hll_key(self, lecture_id: str, timestamp: datetime) -> str:
         """attendance_processor.py:128 (code form) or README.md:105-106 form."""
-        if self.config.hll_key_form == "code":
-            return f"{self.config.hll_key_prefix}{lecture_id}"
-        if timestamp.tzinfo is not None:
-            timestamp = timestamp.astimezone(timezone.utc)
-        return f"{self.config.hll_key_prefix}{lecture_id}:{timestamp.date().isoformat()}"
+        return day_key(self.config.hll_key_prefix, lecture_id,
+                       None if self.config.hll_key_form == "code" else timestamp)
 
     def process_batch(self, messages: Sequence) -> list[dict]:
         """One batch of the loop at attendance_processor.py:100-137.

@@ -10,6 +10,8 @@ import subprocess
 
 import pytest
 
+from facade_stub import StubContext
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -65,22 +67,9 @@ def test_null_context_is_rejected(pkg):
     assert lib.ske_cms_import(None, 0, None, 0, 0) == -1
 
 
-class _StubContext:
-    """Stands where the device context would: records the native calls the
-    facade makes and answers success, so what is checked is what the facade
-    refuses (or accepts) on its own."""
-
-    def __init__(self, lib):
-        self.lib, self.ptr, self.calls = lib, None, []
-
-    def call(self, name, *args):
-        self.calls.append(name)
-        return 0
-
-
 @pytest.fixture
 def stub_client(pkg):
-    ctx = _StubContext(pkg.load_library())
+    ctx = StubContext(pkg.load_library())
     return pkg.SketchClient(decode_responses=True, context=ctx), ctx
 
 
