@@ -28,8 +28,9 @@
  *     after its work on the context stream completed, except ske_swipes_async.
  *   - filters are addressed by a caller-chosen id `fid` < SKE_MAX_FILTERS, HLL
  *     keys by a caller-chosen register-slab slot, Count-Min Sketch tables by a
- *     caller-chosen `cid` < SKE_MAX_CMS.  The facade maps Redis key names to
- *     fids / slots / cids.
+ *     caller-chosen `cid` < SKE_MAX_CMS, heavy-hitter sets by a caller-chosen
+ *     `hid` < SKE_MAX_HH.  The facade maps Redis key names to fids / slots /
+ *     cids.
  */
 #ifndef SKETCH_H
 #define SKETCH_H
@@ -65,6 +66,10 @@ extern "C" {
 #define SKE_ECMSERROR -21    /* "CMS: invalid overestimation value" (CMS.INITBYPROB error) */
 #define SKE_ECMSPROB -22     /* "CMS: invalid prob value" (CMS.INITBYPROB probability) */
 #define SKE_ECMSPARSE -23    /* "CMS: Cannot parse number" */
+#define SKE_EHHNOSET -24     /* heavy-hitter set id not in use */
+#define SKE_EHHEXISTS -25    /* ske_hh_init on an id in use */
+#define SKE_EHHCAP -26       /* capacity_log2 outside [SKE_HH_MIN_LOG2, SKE_HH_MAX_LOG2] */
+#define SKE_EHHSPACE -27     /* ske_hh_list: more entries pass than the output arrays hold */
 
 #define SKE_MEM_HOST 0
 #define SKE_MEM_DEVICE 1
@@ -75,6 +80,12 @@ extern "C" {
 #define SKE_CMS_MAX_DEPTH 64
 #define SKE_CMS_MAX_CELLS (1u << 28) /* width * depth stays below this */
 #define SKE_CMS_MAX_MERGE 64
+#define SKE_MAX_HH 256
+#define SKE_HH_MIN_LOG2 8
+#define SKE_HH_MAX_LOG2 24
+#define SKE_HH_ID_BYTES 16   /* the longest id a heavy-hitter set holds */
+#define SKE_HH_MAX_PROBES 128 /* slots one insert looks at before it gives up */
+#define SKE_HH_LOAD_DEN 2    /* new ids are refused once used >= capacity / SKE_HH_LOAD_DEN */
 #define SKE_HLL_REGISTERS 16384
 #define SKE_HLL_DENSE_BYTES 12288
 
@@ -276,6 +287,63 @@ int ske_cms_merge(ske_ctx *ctx, uint32_t dst, const uint32_t *srcs, const int64_
 int ske_cms_export(ske_ctx *ctx, uint32_t cid, uint32_t *out, uint64_t cap_cells);
 int ske_cms_import(ske_ctx *ctx, uint32_t cid, const uint32_t *in, uint64_t ncells, uint64_t count);
 
+/* ---- heavy hitters beside a Count-Min Sketch table ----
+ * A set of distinct ids (at most SKE_HH_ID_BYTES bytes each) in 2^capacity_log2
+ * device slots, addressed by a caller-chosen hid < SKE_MAX_HH; the context owns
+ * it.  A track adds the ids of a batch whose estimate in table `cid` (CMS.QUERY,
+ * the table as it stands in stream order, so after the batch's adds) reaches
+ * `threshold`; a list reads the members' current estimates back.  The result
+ * depends on the sequence of batches, never on the order inside one: cells only
+ * grow, and an id is judged at the batches it occurs in (an id seen only early,
+ * below the threshold, is not added when later collisions raise its cells).
+ * No reference counterpart in its Redis calls; the lists are those of
+ * attendance_analysis.py:99-118.  RedisBloom's TOPK (HeavyKeeper) draws random
+ * numbers per colliding increment and is not offered.
+ *
+ * Limits: ids with the same 64-bit digest (MurmurHash64A, the Bloom seed; 0
+ * mapped to 1) are one entry, the first to claim the slot names it.  An insert
+ * looks at SKE_HH_MAX_PROBES slots at most and new ids are refused once
+ * capacity / SKE_HH_LOAD_DEN slots are used (a batch in flight may pass that
+ * mark by the claims racing at that moment, never the capacity); a refused id is
+ * dropped and the set's sticky overflow word is set: `complete` is 0 from then
+ * on, until ske_hh_reset.  Entries are never removed one by one.
+ * Guarantee while complete: every id whose true count reaches T, and whose
+ * occurrences all went through a track with threshold <= T, is listed at T --
+ * at its last occurrence its estimate is at least its true count. */
+typedef struct {
+    uint64_t capacity;  /* slots */
+    uint64_t used;      /* ids held */
+    uint64_t overflow;  /* non-zero once an insert was refused */
+} ske_hh_info_t;
+/* SKE_EHHEXISTS when hid is in use, SKE_EHHCAP for a capacity out of range */
+int ske_hh_init(ske_ctx *ctx, uint32_t hid, uint32_t capacity_log2);
+/* SKE_EBUSY while a recorded graph is alive or being recorded */
+int ske_hh_free(ske_ctx *ctx, uint32_t hid);
+/* an empty, complete set again (slots, used and overflow zeroed) */
+int ske_hh_reset(ske_ctx *ctx, uint32_t hid);
+int ske_hh_info(ske_ctx *ctx, uint32_t hid, ske_hh_info_t *out);
+/* Fixed-width ids on the device (id i = the `width` bytes at ids + i * width),
+ * enqueue only and graph-capturable: the form that follows
+ * ske_swipes_fixed_async + ske_cms_add_fixed_async on the same stream.  mask
+ * (may be NULL): only items with mask[i] == want (0 or 1) are looked at.
+ * width > SKE_HH_ID_BYTES: SKE_ETOOLONG; threshold == 0, width == 0 or another
+ * want: SKE_EINVAL; a missing table: SKE_ECMSNOKEY (the table is looked up by
+ * cid at every call). */
+int ske_hh_track_fixed_async(ske_ctx *ctx, uint32_t hid, uint32_t cid, const uint8_t *ids, uint32_t width,
+                             uint64_t n, const uint8_t *mask_or_null, int want, uint32_t threshold);
+/* The packed form (bytes + offs[n + 1]); returns when done.  An id longer than
+ * SKE_HH_ID_BYTES fails the call with SKE_ETOOLONG: with SKE_MEM_HOST before
+ * anything is tracked, with SKE_MEM_DEVICE after the batch's other ids were. */
+int ske_hh_track(ske_ctx *ctx, uint32_t hid, uint32_t cid, const uint8_t *bytes, const uint32_t *offs,
+                 uint64_t n, uint32_t threshold, int mem);
+/* Every member whose current estimate in table cid is >= threshold, sorted by
+ * estimate descending, then id bytes ascending (host arrays: out_ids cap x
+ * SKE_HH_ID_BYTES bytes, zero padded; out_lens and out_est cap entries).
+ * *n_out = how many pass; more than cap: SKE_EHHSPACE and nothing is written
+ * (cap >= used always suffices).  *complete = 0 once an insert was refused. */
+int ske_hh_list(ske_ctx *ctx, uint32_t hid, uint32_t cid, uint32_t threshold, uint8_t *out_ids,
+                uint32_t *out_lens, uint32_t *out_est, uint64_t cap, uint64_t *n_out, int *complete);
+
 /* ---- the fused hot path (K1) ----
  * For every swipe i: v = BF.EXISTS fid id_i; if v: PFADD slot_i id_i.
  *   replaces the per-event pair attendance_processor.py:109-113 + :127-129.
@@ -450,7 +518,8 @@ int ske_ingest_swipes(ske_ctx *ctx, uint32_t fid, const uint8_t *msgs,
 /* ---- stream capture (HIP graphs) ----
  * Record the device work of the calls made between begin and end on the
  * context stream (only enqueue-only calls: ske_swipes_async,
- * ske_swipes_fixed_async, ske_cms_add_fixed_async) into an executable graph, uploaded to the device;
+ * ske_swipes_fixed_async, ske_cms_add_fixed_async, ske_hh_track_fixed_async)
+ * into an executable graph, uploaded to the device;
  * each ske_graph_launch replays it on the context stream.  A consumer that
  * processes a ring of fixed device batch slots replays one graph per turn of
  * the ring instead of one launch per batch (SURVEY.md §8a-1's processor loop at

@@ -39,11 +39,21 @@ SKE_ECMSOVERFLOW = -20
 SKE_ECMSERROR = -21
 SKE_ECMSPROB = -22
 SKE_ECMSPARSE = -23
+SKE_EHHNOSET = -24
+SKE_EHHEXISTS = -25
+SKE_EHHCAP = -26
+SKE_EHHSPACE = -27
 SKE_MEM_HOST = 0
 SKE_MEM_DEVICE = 1
 SKE_MAX_FILTERS = 4096
 SKE_MAX_CMS = 4096
 SKE_CMS_MAX_MERGE = 64
+SKE_MAX_HH = 256
+SKE_HH_MIN_LOG2 = 8
+SKE_HH_MAX_LOG2 = 24
+SKE_HH_ID_BYTES = 16
+SKE_HH_MAX_PROBES = 128
+SKE_HH_LOAD_DEN = 2
 HLL_REGISTERS = 16384
 HLL_DENSE_BYTES = 12288
 
@@ -70,6 +80,10 @@ class BfLink(C.Structure):
 
 class CmsInfo(C.Structure):
     _fields_ = [("width", C.c_uint64), ("depth", C.c_uint64), ("count", C.c_uint64)]
+
+
+class HhInfo(C.Structure):
+    _fields_ = [("capacity", C.c_uint64), ("used", C.c_uint64), ("overflow", C.c_uint64)]
 
 
 class IngestCols(C.Structure):
@@ -142,6 +156,15 @@ SIGNATURES = {
     "ske_cms_merge": (C.c_int, [_CTX, C.c_uint32, _u32p, _vp, C.c_uint32]),
     "ske_cms_export": (C.c_int, [_CTX, C.c_uint32, _u32p, C.c_uint64]),
     "ske_cms_import": (C.c_int, [_CTX, C.c_uint32, _u32p, C.c_uint64, C.c_uint64]),
+    "ske_hh_init": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),
+    "ske_hh_free": (C.c_int, [_CTX, C.c_uint32]),
+    "ske_hh_reset": (C.c_int, [_CTX, C.c_uint32]),
+    "ske_hh_info": (C.c_int, [_CTX, C.c_uint32, C.POINTER(HhInfo)]),
+    "ske_hh_track_fixed_async": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, _u8p, C.c_uint32, C.c_uint64, _u8p,
+                                           C.c_int, C.c_uint32]),
+    "ske_hh_track": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, _u8p, _u32p, C.c_uint64, C.c_uint32, C.c_int]),
+    "ske_hh_list": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_uint32, _u8p, _u32p, _u32p, C.c_uint64,
+                              C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "ske_swipes": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p, C.c_int]),
     "ske_swipes_async": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p]),
     "ske_swipes_fixed": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, C.c_uint32, C.c_uint64, _u8p,

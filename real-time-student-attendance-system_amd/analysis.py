@@ -10,6 +10,12 @@ the host to be grouped.
 
 A Count-Min estimate never undercounts; it overcounts by at most
 ``error * count`` with probability ``1 - probability`` (CMS.INITBYPROB).
+
+The reference's two insights are lists, and the invalid ids are on no roster a
+caller could enumerate.  With ``track_attended`` / ``track_invalid`` set, each
+key gets a heavy-hitter set (client_hh.py, DESIGN.md "Heavy hitters"): every
+batch's ids whose estimate reached the threshold are kept on the device, and
+``top_attended`` / ``top_invalid`` / ``insights`` list them.
 """
 from __future__ import annotations
 
@@ -24,10 +30,21 @@ from .engine import DeviceBuffer
 
 class StudentCounts:
     """Attended / invalid swipe counts per student id, as two CMS keys of a
-    ``SketchClient``."""
+    ``SketchClient``.
+
+    ``track_attended`` / ``track_invalid`` (default None: off, ``update``
+    enqueues exactly the swipes and the two adds): a count from which a
+    student is kept in the key's heavy-hitter set of ``2 ** capacity_log2``
+    slots.  Guarantee, while the listing says ``complete``: every id whose true
+    count reaches ``threshold`` is listed by ``top_*(threshold=threshold)`` for
+    any ``threshold`` at or above the track threshold -- at the batch of its
+    last swipe its estimate was at least its true count, so it joined the set
+    then at the latest, and estimates never fall.  Ids are at most 16 bytes;
+    ids with equal 64-bit digests share one entry."""
 
     def __init__(self, client, attended_key="cms:attended", invalid_key="cms:invalid",
-                 error: float = 0.001, probability: float = 0.01):
+                 error: float = 0.001, probability: float = 0.01, track_attended: int | None = None,
+                 track_invalid: int | None = None, capacity_log2: int = 16):
         self.client = client
         self.attended_key, self.invalid_key = attended_key, invalid_key
         for key in (attended_key, invalid_key):
@@ -35,6 +52,16 @@ class StudentCounts:
                 client.cms_initbyprob(key, error, probability)
             client.keys.expect(encode(key), "cms")  # WRONGTYPE for a key of another kind
         self._bufs = None
+        # per key: (set name, track threshold, the mask value its swipes carry)
+        self._tracks = []
+        for key, thr, want in ((attended_key, track_attended, 1), (invalid_key, track_invalid, 0)):
+            if thr is None:
+                continue
+            if int(thr) < 1:
+                raise ValueError("a track threshold is at least 1")
+            name = b"hh:" + encode(key)
+            client.hh_create(name, key, capacity_log2)
+            self._tracks.append((name, int(thr), want))
 
     def _buffers(self, n: int, width: int):
         b = self._bufs
@@ -77,6 +104,10 @@ class StudentCounts:
         for key, want in ((self.attended_key, 1), (self.invalid_key, 0)):
             cl.ctx.call("ske_cms_add_fixed_async", cl.cms_cid(key), C.c_void_p(d_ids.ptr), width, n,
                         None, C.c_void_p(d_valid.ptr), want)
+        for name, thr, want in self._tracks:  # behind the adds: the estimates include this batch
+            hid, cid = cl._hh_entry(name)
+            cl.ctx.call("ske_hh_track_fixed_async", hid, cid, C.c_void_p(d_ids.ptr), width, n,
+                        C.c_void_p(d_valid.ptr), want, thr)
         cl.ctx.call("ske_sync")
         return d_valid.to_host(np.uint8, n).astype(bool)
 
@@ -97,3 +128,49 @@ class StudentCounts:
     def invalid(self, ids) -> np.ndarray:
         """Estimated invalid attempts of each id."""
         return self._query(self.invalid_key, ids)
+
+    def _top(self, key, k, threshold):
+        name = b"hh:" + encode(key)
+        track = [t for t in self._tracks if t[0] == name]
+        if not track:
+            raise ValueError(f"{key} is not tracked (track_attended / track_invalid)")
+        thr = track[0][1] if threshold is None else int(threshold)
+        if thr < track[0][1]:
+            raise ValueError("a list threshold below the track threshold promises nothing")
+        ids, est, complete = self.client.hh_list(name, thr)
+        if k is not None:
+            ids, est = ids[:k], est[:k]
+        return ids, est, complete
+
+    def top_attended(self, k: int | None = None, threshold: int | None = None):
+        """``(ids, estimates, complete)``: the students whose estimated valid
+        swipes reach ``threshold`` (default: the track threshold), largest
+        first, ties in id order; the first ``k`` of them when ``k`` is given.
+        ``complete`` is False once the set refused an id (it was full): the
+        list may then miss students."""
+        return self._top(self.attended_key, k, threshold)
+
+    def top_invalid(self, k: int | None = None, threshold: int | None = None):
+        """The same over the invalid attempts."""
+        return self._top(self.invalid_key, k, threshold)
+
+    def insights(self, attended_threshold: int | None = None, invalid_threshold: int | None = None) -> list:
+        """The reference's two per-student insights (attendance_analysis.py:
+        105-118), ``data`` as ``{student_id: estimate}`` of the tracked keys.
+        The reference picks its consistent attendees by the median plus the
+        standard deviation of every student's count; a sketch holds no such
+        population, so the caller passes the thresholds (default: the track
+        thresholds).  ``complete`` is added to each entry."""
+        out = []
+        for title, text, key, thr in (
+                ("Most Consistent Attendees", "Students whose estimated attendance reaches the threshold",
+                 self.attended_key, attended_threshold),
+                ("Invalid Attendance Attempts", "Estimated invalid attendance attempts by student id",
+                 self.invalid_key, invalid_threshold)):
+            if not any(t[0] == b"hh:" + encode(key) for t in self._tracks):
+                continue
+            ids, est, complete = self._top(key, None, thr)
+            out.append({"title": title, "description": text,
+                        "data": {i.decode("utf-8", "replace"): int(e) for i, e in zip(ids, est)},
+                        "complete": complete})
+        return out

@@ -34,8 +34,9 @@ Semantics kept from Redis / RedisBloom / redis-py:
     ``PFCOUNT`` of missing keys -> 0; keys of the other type -> WRONGTYPE.
 
 The client is composed per native unit (csrc/sketch_api_*.cpp): the key table
-(keyspace.py), Bloom (client_bloom.py), Count-Min Sketch (client_cms.py), HLL
-(client_hll.py), the fused swipe path (client_swipes.py) and the device ingest
+(keyspace.py), Bloom (client_bloom.py), Count-Min Sketch (client_cms.py),
+heavy-hitter sets beside a CMS key (client_hh.py), HLL (client_hll.py), the
+fused swipe path (client_swipes.py) and the device ingest
 (client_ingest.py); commands.py holds the command table, ``bf()`` / ``cms()``
 and the pipeline.  Here: the constructor, the generic key commands and
 ``execute_command``.
@@ -45,6 +46,7 @@ from __future__ import annotations
 from ._lib import Context
 from .client_bloom import BloomMixin
 from .client_cms import CmsMixin
+from .client_hh import HhMixin
 from .client_hll import HllMixin
 from .client_ingest import IngestMixin
 from .client_swipes import SwipesMixin
@@ -56,7 +58,7 @@ from .keyspace import (BF_TYPE_NAME, CMS_TYPE_NAME, KIND_TYPE_NAMES, TYPE_NAME_K
                        KeySpace, redis_glob)
 
 
-class SketchClient(BloomMixin, CmsMixin, HllMixin, SwipesMixin, IngestMixin):
+class SketchClient(BloomMixin, CmsMixin, HhMixin, HllMixin, SwipesMixin, IngestMixin):
     """Drop-in for ``redis.Redis`` on the reference's Bloom + HLL calls."""
 
     def __init__(self, host: str = "localhost", port: int = 6379, db: int = 0,
@@ -67,6 +69,7 @@ class SketchClient(BloomMixin, CmsMixin, HllMixin, SwipesMixin, IngestMixin):
         self.keys = KeySpace(self.ctx)
         self.host, self.port, self.db = host, port, db
         self._ingest = None  # client_ingest.IngestState, made by the first ingest
+        self._hh_init_registry()
 
     # ------------------------------------------------------------ helpers
     def _ok(self):
@@ -87,6 +90,9 @@ class SketchClient(BloomMixin, CmsMixin, HllMixin, SwipesMixin, IngestMixin):
 
     # ------------------------------------------------------------ generic keys
     def delete(self, *names) -> int:
+        if self._hh:  # heavy-hitter sets go with the CMS key they read
+            for n in names:
+                self._hh_release(encode(n))
         return sum(self.keys.drop(encode(n)) for n in names)
 
     def exists(self, *names) -> int:
@@ -113,6 +119,8 @@ class SketchClient(BloomMixin, CmsMixin, HllMixin, SwipesMixin, IngestMixin):
         return self._s(KIND_TYPE_NAMES.get(self.keys.type_of(encode(name)), "none"))
 
     def flushall(self, *_a, **_k) -> bool:
+        if self._hh:
+            self._hh_release(None)
         for key in list(self.keys.kind):
             self.keys.drop(key)
         return True

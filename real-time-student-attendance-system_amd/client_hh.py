@@ -1,0 +1,81 @@
+"""The heavy-hitter half of ``SketchClient`` (csrc/sketch_api_hh.cpp): sets of
+ids whose Count-Min estimate reached a threshold, each bound to a CMS key.
+
+A set is no Redis key -- it has no kind, no TYPE reply and no command in
+``execute_command`` (RedisBloom's own TOPK cannot be matched bit for bit,
+DESIGN.md "Heavy hitters") -- so the client keeps its own registry of live
+sets, by name.  ``DEL`` of the bound CMS key and ``FLUSHALL`` free them; while
+no set exists neither makes any further native call."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+from ._lib import SKE_MEM_HOST, ptr as _ptr
+from .encoding import encode
+from .engine import hh_info, hh_list
+from .exceptions import ResponseError
+
+
+class HhMixin:
+    def _hh_init_registry(self) -> None:
+        self._hh: dict[bytes, tuple[int, bytes]] = {}  # set name -> (hid, the CMS key it reads)
+        self._hh_free_ids = list(range(_lib.SKE_MAX_HH - 1, -1, -1))
+
+    def hh_create(self, name, cms_key, capacity_log2: int = 16) -> int:
+        """A new, empty set of 2^capacity_log2 slots bound to an existing CMS
+        key; returns its native id."""
+        name, key = encode(name), encode(cms_key)
+        if name in self._hh:
+            raise ResponseError(_lib.strerror(_lib.SKE_EHHEXISTS))
+        self.cms_cid(key)  # the key must exist and be a CMS key
+        if not self._hh_free_ids:
+            raise ResponseError("ERR too many heavy-hitter sets on this device")
+        if not _lib.SKE_HH_MIN_LOG2 <= int(capacity_log2) <= _lib.SKE_HH_MAX_LOG2:
+            raise ResponseError(_lib.strerror(_lib.SKE_EHHCAP))
+        hid = self._hh_free_ids[-1]
+        self.ctx.call("ske_hh_init", hid, int(capacity_log2))
+        self._hh_free_ids.pop()
+        self._hh[name] = (hid, key)
+        return hid
+
+    def _hh_entry(self, name) -> tuple[int, int]:
+        """(hid, cid) of a live set; the bound key is looked up now."""
+        e = self._hh.get(encode(name))
+        if e is None:
+            raise ResponseError(_lib.strerror(_lib.SKE_EHHNOSET))
+        return e[0], self.cms_cid(e[1])
+
+    def hh_free(self, name) -> bool:
+        e = self._hh.pop(encode(name), None)
+        if e is None:
+            return False
+        self.ctx.call("ske_hh_free", e[0])
+        self._hh_free_ids.append(e[0])
+        return True
+
+    def _hh_release(self, cms_key: bytes | None) -> None:
+        """Free the sets bound to a key that is going away (None: all)."""
+        for name in [n for n, (_, k) in self._hh.items() if cms_key is None or k == cms_key]:
+            self.hh_free(name)
+
+    def hh_reset(self, name) -> None:
+        self.ctx.call("ske_hh_reset", self._hh_entry(name)[0])
+
+    def hh_info(self, name) -> dict:
+        return hh_info(self.ctx, self._hh_entry(name)[0])
+
+    def hh_track_packed(self, name, buf: np.ndarray, offs: np.ndarray, threshold: int) -> None:
+        """Every id of the packed batch whose estimate in the bound key is at
+        least ``threshold`` joins the set (after the batch's own adds)."""
+        hid, cid = self._hh_entry(name)
+        n = len(offs) - 1
+        if n > 0:
+            self.ctx.call("ske_hh_track", hid, cid, _ptr(np.ascontiguousarray(buf, np.uint8)),
+                          _ptr(np.ascontiguousarray(offs, np.uint32)), n, int(threshold), SKE_MEM_HOST)
+
+    def hh_list(self, name, threshold: int):
+        """``(ids, estimates, complete)``: the members whose current estimate
+        is at least ``threshold``, largest first (engine.hh_list)."""
+        hid, cid = self._hh_entry(name)
+        return hh_list(self.ctx, hid, cid, threshold)

@@ -14,13 +14,11 @@ void free_cms(Cms &T) {
     T = Cms{};
 }
 
-}  // namespace ske
-
-static Cms *get_cms(ske_ctx *c, uint32_t cid) {
+Cms *get_cms(ske_ctx *c, uint32_t cid) {
     return cid < c->cms.size() && c->cms[cid].cells ? &c->cms[cid] : nullptr;
 }
 
-static CmsTable table_of(const Cms &T) {
+CmsTable table_of(const Cms &T) {
     CmsTable D{};
     D.cells = T.cells;
     D.count = T.count;
@@ -29,6 +27,8 @@ static CmsTable table_of(const Cms &T) {
     D.ncells = T.width * T.depth;
     return D;
 }
+
+}  // namespace ske
 
 // the bulk form of this table: private LDS tables up to the threshold
 static bool cms_use_lds(const ske_ctx *c, const Cms &T) {

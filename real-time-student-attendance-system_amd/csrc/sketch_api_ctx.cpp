@@ -1,7 +1,7 @@
 // sketch_api_ctx.cpp -- libsketch C-ABI (include/sketch.h): the context's
 // lifecycle, options, the sticky error word, streams, host -> device staging,
 // pass timing, the scratch-use ordering and graph capture.  The other
-// subsystems are sketch_api_{bloom,hll,swipes,ingest,cms}.cpp (map: sketch_ctx.h).
+// subsystems are sketch_api_{bloom,hll,swipes,ingest,cms,hh}.cpp (map: sketch_ctx.h).
 #include <stdlib.h>
 #include <string.h>
 
@@ -292,6 +292,10 @@ const char *ske_strerror(int code) {
     case SKE_ECMSERROR: return "CMS: invalid overestimation value";
     case SKE_ECMSPROB: return "CMS: invalid prob value";
     case SKE_ECMSPARSE: return "CMS: Cannot parse number";
+    case SKE_EHHNOSET: return "ERR heavy-hitter set does not exist";
+    case SKE_EHHEXISTS: return "ERR heavy-hitter set already exists";
+    case SKE_EHHCAP: return "ERR heavy-hitter capacity out of range";
+    case SKE_EHHSPACE: return "ERR heavy-hitter list does not fit the output";
     default: return "ERR unknown";
     }
 }
@@ -329,6 +333,10 @@ int ske_open(int device, ske_ctx **out) {
         const unsigned long long cells = strtoull(v, nullptr, 10);
         if (cells < c->cms_lds_cells) c->cms_lds_cells = uint32_t(cells);
     }
+    if (const char *v = getenv("SKE_HH_LDS_CELLS")) {
+        const unsigned long long cells = strtoull(v, nullptr, 10);
+        c->hh_lds_cells = cells < kCmsLdsCells ? uint32_t(cells) : kCmsLdsCells;
+    }
     if (hipMalloc(&c->zero16, 64) != hipSuccess || hipMemset(c->zero16, 0, 64) != hipSuccess) {
         ske_close(c);
         return SKE_ENOMEM;
@@ -343,6 +351,7 @@ int ske_close(ske_ctx *c) {
     if (c->st) (void)hipStreamSynchronize(c->st);
     for (auto &F : c->filters) free_filter(F);
     for (auto &T : c->cms) free_cms(T);
+    for (auto &H : c->hh) free_hh(H);
     if (c->regs) (void)hipFree(c->regs);
     if (c->tau) (void)hipFree(c->tau);
     if (c->sig) (void)hipFree(c->sig);

@@ -10,7 +10,7 @@
 //           the table in memory;
 //   global  one atomic per (item, row).
 // Every add to the table in memory is cms_sat_add below.
-#include "sketch_internal.h"
+#include "sketch_cms_dev.h"
 
 namespace ske {
 namespace {
@@ -27,17 +27,6 @@ constexpr int kCmsBlock = 256;
 __device__ __forceinline__ void cms_sat_add(uint32_t *cell, uint32_t v) {
     const uint32_t old = atomicAdd(cell, v);
     if (old + v < old) atomicMax(cell, 0xffffffffu);
-}
-
-__device__ __forceinline__ Item cms_item(const CmsItems &I, uint32_t i) {
-    if (I.offs) return load_item(I.bytes, I.offs[i], I.offs[i + 1]);
-    return load_item(I.bytes + uint64_t(i) * I.fixed_w, 0, I.fixed_w);
-}
-
-// the item's cell index in row r of the whole table
-__device__ __forceinline__ uint32_t cms_cell(const CmsTable &T, const Item &it, uint32_t r) {
-    const uint32_t h = it.len <= 16 ? murmur2_32_words(it.w0, it.w1, it.len, r) : murmur2_32(it.p, it.len, r);
-    return r * T.div.d + fastmod32(h, T.div);
 }
 
 // does item i count, and by how much (0: skip it)

@@ -85,6 +85,31 @@ __device__ __forceinline__ uint64_t murmur_item(const Item &it, uint64_t seed) {
     return mm_final(h);
 }
 
+// murmur_item for an item of at most 16 bytes from its two words alone (no
+// memory access; host-callable).
+SKE_HD uint64_t murmur_words(uint64_t w0, uint64_t w1, uint32_t len, uint64_t seed) {
+    uint64_t h = seed ^ (uint64_t(len) * kMurmurM);
+    const uint32_t nblk = len >> 3;
+    if (nblk >= 1) h = mm_block(h, w0);
+    if (nblk >= 2) h = mm_block(h, w1);
+    if (len & 7) {
+        h ^= nblk == 0 ? w0 : w1;
+        h *= kMurmurM;
+    }
+    return mm_final(h);
+}
+
+// Heavy-hitter sets (sketch_hh.hip): an id's claim word is its digest -- the
+// Bloom path's hash of the id bytes, 0 (the empty slot) mapped to 1 -- and its
+// probe path starts at the digest's low bits.
+SKE_HD uint64_t hh_digest(uint64_t w0, uint64_t w1, uint32_t len) {
+    const uint64_t d = murmur_words(w0, w1, len, kBloomSeed);
+    return d ? d : 1;
+}
+SKE_HD uint32_t hh_start(uint64_t digest, uint32_t capacity_log2) {
+    return uint32_t(digest) & ((1u << capacity_log2) - 1);
+}
+
 // MurmurHash64A of an item of at most 8 bytes held in w (zero padded).
 SKE_HD uint64_t murmur_short(uint64_t w, uint32_t len, uint64_t seed) {
     uint64_t h = seed ^ (uint64_t(len) * kMurmurM);

@@ -9,6 +9,7 @@
 //   sketch_api_swipes.cpp  K1: variant choice, launch_k1, ske_swipes*, ske_route_*
 //   sketch_api_ingest.cpp  ingest, the key table, the generator
 //   sketch_api_cms.cpp     Count-Min Sketch tables: init, add, query, merge, export / import
+//   sketch_api_hh.cpp      heavy-hitter sets beside a table: init, track, list
 // A helper used by one unit is static there; what crosses units is declared here.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -53,6 +54,14 @@ struct Cms {
     Div32 div{};
 };
 
+// one heavy-hitter set (base == nullptr: the hid is free); one allocation:
+// a 16-byte head (used, overflow), then the claim words, the id words, the lengths
+struct Hh {
+    uint8_t *base = nullptr;
+    size_t bytes = 0;
+    uint32_t log2 = 0;
+};
+
 struct Staged {
     const uint8_t *bytes = nullptr;
     const uint32_t *offs = nullptr;
@@ -80,6 +89,11 @@ struct ske_ctx {
     // tables up to this many cells take the LDS form (the environment variable
     // SKE_CMS_LDS_CELLS, read by ske_open, lowers it for A/B timing; 0: never)
     uint32_t cms_lds_cells = ske::kCmsLdsCells;
+    std::vector<ske::Hh> hh;    // by hid (sized on first use)
+    bool hh_lds_ready = false;  // hh_setup() done (first ske_hh_init)
+    // a track copies tables up to this many cells into LDS (SKE_HH_LDS_CELLS,
+    // read by ske_open, sets it for A/B timing, at most kCmsLdsCells; 0: never)
+    uint32_t hh_lds_cells = ske::kHhLdsCells;
     uint8_t *regs = nullptr;  // nslots * 16384
     uint32_t nslots = 0;
     double *tau = nullptr, *sig = nullptr;  // device estimator tables (lazy)
@@ -229,6 +243,12 @@ const ChainDev &chain_of(Filter *F);
 
 // ---- sketch_api_cms.cpp
 void free_cms(Cms &T);
+// the table of a cid in use, else nullptr; its kernel view
+Cms *get_cms(ske_ctx *c, uint32_t cid);
+CmsTable table_of(const Cms &T);
+
+// ---- sketch_api_hh.cpp
+void free_hh(Hh &H);
 
 // ---- sketch_api_swipes.cpp
 bool use_lds(const ske_ctx *c, const ChainDev &ch);

@@ -218,6 +218,32 @@ hipError_t launch_cms_query(const CmsTable &T, const CmsItems &I, uint32_t *out,
 // write == false: only the range check into M.flag; true: dst = the weighted sums
 hipError_t launch_cms_merge(const CmsMergeArgs &M, bool write, int cus, hipStream_t st);
 
+// sketch_hh.hip -- heavy-hitter sets beside a Count-Min Sketch table: ids whose
+// estimate reached a threshold, in an insert-only open-addressing table
+constexpr uint32_t kHhMaxProbes = 128;  // slots one insert looks at (SKE_HH_MAX_PROBES)
+constexpr uint32_t kHhLoadDen = 2;      // new claims stop at capacity / kHhLoadDen (SKE_HH_LOAD_DEN)
+// tables up to this many cells are copied into LDS by every workgroup of a
+// track and queried there; larger ones (and all, when 0) are read from memory
+constexpr uint32_t kHhLdsCells = kCmsLdsCells;
+struct HhSet {
+    unsigned long long *claim;  // per slot: the id's digest (hh_digest), 0 = empty
+    uint64_t *ids;              // per slot: w0, w1 of the id (Item), written by the claim's winner
+    uint32_t *len;              // per slot: the id's length
+    unsigned int *used;         // slots claimed
+    unsigned int *overflow;     // sticky: an insert was refused
+    uint32_t mask;              // capacity - 1
+    uint32_t limit;             // capacity / kHhLoadDen
+};
+hipError_t hh_setup();
+// every item (mask as CmsItems) whose estimate in T is >= threshold joins S;
+// toolong (may be null): set when an item is longer than 16 bytes (it is skipped)
+hipError_t launch_hh_track(const CmsTable &T, const CmsItems &I, const HhSet &S, uint32_t threshold, bool lds,
+                           unsigned int *toolong, int cus, hipStream_t st);
+// members with estimate >= threshold, unordered: entry j < min(*out_n, cap) in
+// out_ids[2j..], out_len[j], out_est[j]; *out_n (zeroed by the caller) counts all that pass
+hipError_t launch_hh_list(const CmsTable &T, const HhSet &S, uint32_t threshold, uint32_t cap, uint64_t *out_ids,
+                          uint32_t *out_len, uint32_t *out_est, unsigned int *out_n, hipStream_t st);
+
 // sketch_order.hip -- order-exact paths (replies that depend on item order)
 struct Scratch;  // growable device scratch, owned by the context
 constexpr int kScratchSlots = 48;
@@ -303,6 +329,10 @@ enum StageSlot : int {
     kStgCmsIncr,   // ske_cms_incrby: an increment per item
     kStgCmsReply,  // ske_cms_incrby / ske_cms_query: a u32 reply per item on its way to the host
     kStgCmsFlag,   // ske_cms_merge: the overflow word of the check pass, then the sources' counts
+    kStgHhFlag,    // ske_hh_track: the too-long word | ske_hh_list: the count of entries that pass
+    kStgHhIds,     // ske_hh_list: the entries' id words,
+    kStgHhLen,     //   lengths,
+    kStgHhEst,     //   estimates
     kStageSlotCount
 };
 

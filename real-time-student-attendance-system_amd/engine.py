@@ -13,7 +13,7 @@ import gc
 
 import numpy as np
 
-from ._lib import CmsInfo, Context, GenParams, SKE_MEM_DEVICE
+from ._lib import CmsInfo, Context, GenParams, HhInfo, SKE_HH_ID_BYTES, SKE_MEM_DEVICE
 from . import synthetic
 
 PASS_KINDS = 9  # SKE_PASS_KINDS (include/sketch.h)
@@ -60,6 +60,32 @@ class DeviceBuffer:
         if a.nbytes:
             self.ctx.call("ske_memcpy", C.c_void_p(self.ptr), a.ctypes.data_as(C.c_void_p),
                           a.nbytes, 0)
+
+
+def hh_info(ctx: Context, hid: int) -> dict:
+    """ske_hh_info: capacity, used and the sticky overflow word."""
+    info = HhInfo()
+    ctx.call("ske_hh_info", int(hid), C.byref(info))
+    return {"capacity": int(info.capacity), "used": int(info.used), "overflow": int(info.overflow)}
+
+
+def hh_list(ctx: Context, hid: int, cid: int, threshold: int, room: int | None = None):
+    """ske_hh_list: ``(ids, estimates, complete)`` -- the members of set
+    ``hid`` whose current estimate in table ``cid`` is at least ``threshold``,
+    as bytes, sorted by estimate descending, then id bytes ascending, their
+    estimates (u32), and whether the set ever refused an insert.  ``room``:
+    entries the output holds (default: the set's ``used``, always enough)."""
+    if room is None:
+        room = hh_info(ctx, hid)["used"]
+    room = max(int(room), 1)
+    ids = np.zeros((room, SKE_HH_ID_BYTES), np.uint8)
+    lens = np.zeros(room, np.uint32)
+    est = np.zeros(room, np.uint32)
+    n, complete = C.c_uint64(0), C.c_int(1)
+    ctx.call("ske_hh_list", int(hid), int(cid), int(threshold), ids.ctypes.data_as(C.c_void_p),
+             lens.ctypes.data_as(C.c_void_p), est.ctypes.data_as(C.c_void_p), room, C.byref(n), C.byref(complete))
+    k = int(n.value)
+    return [ids[i, :lens[i]].tobytes() for i in range(k)], est[:k].copy(), bool(complete.value)
 
 
 class SweBatch(C.Structure):
@@ -302,6 +328,39 @@ class SketchEngine:
         out = np.zeros((info.depth, info.width), np.uint32)
         self.ctx.call("ske_cms_export", int(cid), out.ctypes.data_as(C.c_void_p), out.size)
         return out, int(info.count)
+
+    # ---- heavy hitters beside a Count-Min Sketch table
+    def hh_init(self, hid: int, capacity_log2: int):
+        self.ctx.call("ske_hh_init", int(hid), int(capacity_log2))
+
+    def hh_free(self, hid: int):
+        self.ctx.call("ske_hh_free", int(hid))
+
+    def hh_reset(self, hid: int):
+        self.ctx.call("ske_hh_reset", int(hid))
+
+    def hh_info(self, hid: int) -> dict:
+        return hh_info(self.ctx, hid)
+
+    def hh_track(self, hid: int, cid: int, b: DeviceBatch, threshold: int, mask: DeviceBuffer | None = None,
+                 want: int = 1):
+        """Every id of the resident batch (with ``mask``: those whose mask
+        byte equals ``want``) whose estimate in table ``cid`` is at least
+        ``threshold`` joins set ``hid``.  A fixed-width batch is only enqueued
+        (ske_hh_track_fixed_async, behind the batch's cms_add on the same
+        stream, capturable; ``sync()`` waits); a batch of bytes + offsets goes
+        through ske_hh_track, which takes no mask and returns when done."""
+        if b.width > 0:
+            self.ctx.call("ske_hh_track_fixed_async", int(hid), int(cid), C.c_void_p(b.bytes.ptr), b.width, b.n,
+                          C.c_void_p(mask.ptr) if mask else None, int(want), int(threshold))
+            return
+        if mask is not None:
+            raise ValueError("a masked track needs a fixed-width batch")
+        self.ctx.call("ske_hh_track", int(hid), int(cid), C.c_void_p(b.bytes.ptr), C.c_void_p(b.offs.ptr), b.n,
+                      int(threshold), SKE_MEM_DEVICE)
+
+    def hh_list(self, hid: int, cid: int, threshold: int):
+        return hh_list(self.ctx, hid, cid, threshold)
 
     # ---- HIP graphs: record enqueue-only calls once, replay many times
     def capture(self, fn) -> "Graph":
