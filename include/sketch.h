@@ -29,7 +29,8 @@
  *   - filters are addressed by a caller-chosen id `fid` < SKE_MAX_FILTERS, HLL
  *     keys by a caller-chosen register-slab slot, Count-Min Sketch tables by a
  *     caller-chosen `cid` < SKE_MAX_CMS, heavy-hitter sets by a caller-chosen
- *     `hid` < SKE_MAX_HH.  The facade maps Redis key names to fids / slots /
+ *     `hid` < SKE_MAX_HH, time profiles by a caller-chosen `tid` < SKE_MAX_TP.
+ *     The facade maps Redis key names to fids / slots /
  *     cids.
  */
 #ifndef SKETCH_H
@@ -70,6 +71,9 @@ extern "C" {
 #define SKE_EHHEXISTS -25    /* ske_hh_init on an id in use */
 #define SKE_EHHCAP -26       /* capacity_log2 outside [SKE_HH_MIN_LOG2, SKE_HH_MAX_LOG2] */
 #define SKE_EHHSPACE -27     /* ske_hh_list: more entries pass than the output arrays hold */
+/* -28 is not assigned */
+#define SKE_ETPNOSET -29     /* time profile id not in use */
+#define SKE_ETPEXISTS -30    /* ske_tp_init on an id in use */
 
 #define SKE_MEM_HOST 0
 #define SKE_MEM_DEVICE 1
@@ -86,6 +90,8 @@ extern "C" {
 #define SKE_HH_ID_BYTES 16   /* the longest id a heavy-hitter set holds */
 #define SKE_HH_MAX_PROBES 128 /* slots one insert looks at before it gives up */
 #define SKE_HH_LOAD_DEN 2    /* new ids are refused once used >= capacity / SKE_HH_LOAD_DEN */
+#define SKE_MAX_TP 256
+#define SKE_TP_BINS 168      /* weekday * 24 + hour, Monday = 0 */
 #define SKE_HLL_REGISTERS 16384
 #define SKE_HLL_DENSE_BYTES 12288
 
@@ -344,6 +350,38 @@ int ske_hh_track(ske_ctx *ctx, uint32_t hid, uint32_t cid, const uint8_t *bytes,
 int ske_hh_list(ske_ctx *ctx, uint32_t hid, uint32_t cid, uint32_t threshold, uint8_t *out_ids,
                 uint32_t *out_lens, uint32_t *out_est, uint64_t cap, uint64_t *n_out, int *complete);
 
+/* ---- time profile: weekday x hour counters of the swipes' times ----
+ * SKE_TP_BINS u64 counters on the device, addressed by a caller-chosen tid <
+ * SKE_MAX_TP; the context owns them.  A swipe's time is an int64_t `epoch`,
+ * seconds since 1970-01-01T00:00:00 UTC; every value is legal.  By floor
+ * division (a negative epoch does not truncate toward zero):
+ *   day = floor(epoch / 86400), sod = epoch - day * 86400 in [0, 86400),
+ *   hour = sod / 3600, dow = (day + 3) mod 7 in [0, 7) with Monday = 0
+ *   (datetime.weekday(); 1970-01-01 was a Thursday), bin = dow * 24 + hour.
+ * No reference counterpart in its Redis calls: "Attendance by Day"
+ * (attendance_analysis.py:77-85) is the counters summed per weekday, and the
+ * late bytes turn ske_cms_add_fixed_async / ske_hh_track_fixed_async into the
+ * counters of "Habitual Latecomers" (:65-75). */
+int ske_tp_init(ske_ctx *ctx, uint32_t tid);  /* zeroed; SKE_ETPEXISTS when tid is in use */
+/* SKE_EBUSY while a recorded graph is alive or being recorded */
+int ske_tp_free(ske_ctx *ctx, uint32_t tid);
+int ske_tp_reset(ske_ctx *ctx, uint32_t tid); /* every counter zero again */
+/* the counters into a host array of SKE_TP_BINS entries; returns when done */
+int ske_tp_read(ske_ctx *ctx, uint32_t tid, uint64_t *out168);
+/* overwrite the counters from a host array (restore; the sum of several ranks'
+ * profiles, formed on the host) */
+int ske_tp_import(ske_ctx *ctx, uint32_t tid, const uint64_t *in168);
+/* One batch of times on the device (epoch 8-byte aligned), enqueue only and
+ * graph-capturable.  counts[bin(epoch[i])] += 1 for every i the mask lets
+ * through (mask NULL, or mask[i] == want, want 0 or 1).  late (may be NULL):
+ * late[i] = sod(epoch[i]) >= late_from ? 1 : 0 for EVERY i, whatever the mask
+ * says (the reference counts valid and invalid rows alike); late_from in
+ * [0, 86400], 86400: nobody is late.  n == 0 only checks the arguments.
+ * Another want, late_from > 86400, n >= 2^32 - 1 or epoch NULL with n > 0:
+ * SKE_EINVAL; a tid not in use: SKE_ETPNOSET. */
+int ske_tp_add_async(ske_ctx *ctx, uint32_t tid, const int64_t *epoch, uint64_t n,
+                     const uint8_t *mask_or_null, int want, uint32_t late_from, uint8_t *late_or_null);
+
 /* ---- the fused hot path (K1) ----
  * For every swipe i: v = BF.EXISTS fid id_i; if v: PFADD slot_i id_i.
  *   replaces the per-event pair attendance_processor.py:109-113 + :127-129.
@@ -518,8 +556,8 @@ int ske_ingest_swipes(ske_ctx *ctx, uint32_t fid, const uint8_t *msgs,
 /* ---- stream capture (HIP graphs) ----
  * Record the device work of the calls made between begin and end on the
  * context stream (only enqueue-only calls: ske_swipes_async,
- * ske_swipes_fixed_async, ske_cms_add_fixed_async, ske_hh_track_fixed_async)
- * into an executable graph, uploaded to the device;
+ * ske_swipes_fixed_async, ske_cms_add_fixed_async, ske_hh_track_fixed_async,
+ * ske_tp_add_async) into an executable graph, uploaded to the device;
  * each ske_graph_launch replays it on the context stream.  A consumer that
  * processes a ring of fixed device batch slots replays one graph per turn of
  * the ring instead of one launch per batch (SURVEY.md §8a-1's processor loop at

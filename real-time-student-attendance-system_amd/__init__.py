@@ -7,7 +7,7 @@ attendance_processor.py:152), executed by hand-written gfx950 HIP kernels in
 """
 from . import exceptions
 from ._lib import Context, SketchLibError, load as load_library, LIB_PATH
-from .analysis import StudentCounts
+from .analysis import StudentCounts, epoch_seconds
 from .client import BloomCommands, CMSCommands, Pipeline, Redis, SketchClient
 from .config import AttendanceConfig
 from .encoding import encode, pack, pack_ints
@@ -17,6 +17,6 @@ from .processor import AttendanceProcessor, campus_rollup, lecture_rankings
 __all__ = [
     "AttendanceConfig", "AttendanceProcessor", "BloomCommands", "CMSCommands", "Context", "DataError",
     "LIB_PATH", "Pipeline", "Redis", "RedisError", "ResponseError", "SketchClient",
-    "SketchLibError", "StudentCounts", "campus_rollup", "encode", "exceptions", "lecture_rankings",
-    "load_library", "pack", "pack_ints",
+    "SketchLibError", "StudentCounts", "campus_rollup", "encode", "epoch_seconds", "exceptions",
+    "lecture_rankings", "load_library", "pack", "pack_ints",
 ]

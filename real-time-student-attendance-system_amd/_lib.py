@@ -43,6 +43,8 @@ SKE_EHHNOSET = -24
 SKE_EHHEXISTS = -25
 SKE_EHHCAP = -26
 SKE_EHHSPACE = -27
+SKE_ETPNOSET = -29
+SKE_ETPEXISTS = -30
 SKE_MEM_HOST = 0
 SKE_MEM_DEVICE = 1
 SKE_MAX_FILTERS = 4096
@@ -54,6 +56,8 @@ SKE_HH_MAX_LOG2 = 24
 SKE_HH_ID_BYTES = 16
 SKE_HH_MAX_PROBES = 128
 SKE_HH_LOAD_DEN = 2
+SKE_MAX_TP = 256
+SKE_TP_BINS = 168
 HLL_REGISTERS = 16384
 HLL_DENSE_BYTES = 12288
 
@@ -165,6 +169,12 @@ SIGNATURES = {
     "ske_hh_track": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, _u8p, _u32p, C.c_uint64, C.c_uint32, C.c_int]),
     "ske_hh_list": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_uint32, _u8p, _u32p, _u32p, C.c_uint64,
                               C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "ske_tp_init": (C.c_int, [_CTX, C.c_uint32]),
+    "ske_tp_free": (C.c_int, [_CTX, C.c_uint32]),
+    "ske_tp_reset": (C.c_int, [_CTX, C.c_uint32]),
+    "ske_tp_read": (C.c_int, [_CTX, C.c_uint32, _u64p]),
+    "ske_tp_import": (C.c_int, [_CTX, C.c_uint32, _u64p]),
+    "ske_tp_add_async": (C.c_int, [_CTX, C.c_uint32, _vp, C.c_uint64, _u8p, C.c_int, C.c_uint32, _u8p]),
     "ske_swipes": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p, C.c_int]),
     "ske_swipes_async": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p]),
     "ske_swipes_fixed": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, C.c_uint32, C.c_uint64, _u8p,

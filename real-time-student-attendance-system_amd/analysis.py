@@ -16,16 +16,55 @@ caller could enumerate.  With ``track_attended`` / ``track_invalid`` set, each
 key gets a heavy-hitter set (client_hh.py, DESIGN.md "Heavy hitters"): every
 batch's ids whose estimate reached the threshold are kept on the device, and
 ``top_attended`` / ``top_invalid`` / ``insights`` list them.
+
+"Habitual Latecomers" (:65-75) and "Attendance by Day" (:77-85) need each
+swipe's time.  With ``late_key`` / ``day_profile`` set, ``update`` takes the
+times too: a time profile (client_tp.py, DESIGN.md "Time profile") counts the
+swipes per weekday and hour and marks the late ones on the device, and that
+mark is the mask of a third Count-Min key, the late swipes per student.
 """
 from __future__ import annotations
 
 import ctypes as C
+from datetime import datetime, timedelta, timezone
 
 import numpy as np
 
 from ._lib import SKE_MEM_DEVICE
 from .encoding import encode, pack
 from .engine import DeviceBuffer
+
+
+DAY_NAMES = ("Monday", "Tuesday", "Wednesday", "Thursday", "Friday", "Saturday", "Sunday")
+_EPOCH = datetime(1970, 1, 1)
+_EPOCH_UTC = datetime(1970, 1, 1, tzinfo=timezone.utc)
+_SECOND = timedelta(seconds=1)
+
+
+def epoch_seconds(times) -> np.ndarray:
+    """Swipe times as int64 seconds since 1970-01-01T00:00:00 UTC, floored.
+
+    An integer array is taken as it is; a ``datetime64`` array of any unit is
+    floored to seconds; a sequence of ``datetime`` objects: a naive one is UTC
+    as written, an aware one is converted to UTC, fractions are floored (also
+    before 1970).  This is what Cassandra keeps of the timestamps the
+    reference's processor inserts (attendance_processor.py:106, :116-124), and
+    the convention of the ingest kernel's UTC day."""
+    a = times if isinstance(times, np.ndarray) else np.asarray(times)
+    if a.size == 0:
+        return np.zeros(0, np.int64)
+    if a.dtype.kind in "iu":
+        return np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+    if a.dtype.kind == "M":
+        return np.ascontiguousarray(a.astype("datetime64[s]").astype(np.int64)).reshape(-1)
+    if a.dtype.kind != "O":
+        raise TypeError("times are int64 seconds, datetime64 values or datetime objects")
+    out = np.empty(a.size, np.int64)
+    for i, t in enumerate(a.reshape(-1)):
+        if not isinstance(t, datetime):
+            raise TypeError("times are int64 seconds, datetime64 values or datetime objects")
+        out[i] = (t - (_EPOCH if t.tzinfo is None else _EPOCH_UTC)) // _SECOND
+    return out
 
 
 class StudentCounts:
@@ -40,14 +79,28 @@ class StudentCounts:
     any ``threshold`` at or above the track threshold -- at the batch of its
     last swipe its estimate was at least its true count, so it joined the set
     then at the latest, and estimates never fall.  Ids are at most 16 bytes;
-    ids with equal 64-bit digests share one entry."""
+    ids with equal 64-bit digests share one entry.
+
+    ``late_key`` (default None: off): a third CMS key that counts, per
+    student, the swipes -- valid or not, as the reference counts them -- whose
+    UTC second of the day is at least ``late_from``; ``track_late`` keeps its
+    heavy-hitter set.  ``day_profile``: the name of a time profile
+    (``client.tp_create``; made here when it does not exist) that counts every
+    swipe by weekday and hour.  With either set ``update`` needs the swipes'
+    times; with only ``late_key`` the profile is named ``b"tp:" + late_key``."""
 
     def __init__(self, client, attended_key="cms:attended", invalid_key="cms:invalid",
                  error: float = 0.001, probability: float = 0.01, track_attended: int | None = None,
-                 track_invalid: int | None = None, capacity_log2: int = 16):
+                 track_invalid: int | None = None, capacity_log2: int = 16, late_key=None,
+                 late_from: int = 9 * 3600, track_late: int | None = None, day_profile=None):
         self.client = client
         self.attended_key, self.invalid_key = attended_key, invalid_key
-        for key in (attended_key, invalid_key):
+        self.late_key, self.late_from = late_key, int(late_from)
+        if not 0 <= self.late_from <= 86400:
+            raise ValueError("late_from is a second of the day, 0 to 86400")
+        if track_late is not None and late_key is None:
+            raise ValueError("track_late needs a late_key")
+        for key in (attended_key, invalid_key) + ((late_key,) if late_key is not None else ()):
             if client.keys.type_of(encode(key)) is None:
                 client.cms_initbyprob(key, error, probability)
             client.keys.expect(encode(key), "cms")  # WRONGTYPE for a key of another kind
@@ -62,6 +115,20 @@ class StudentCounts:
             name = b"hh:" + encode(key)
             client.hh_create(name, key, capacity_log2)
             self._tracks.append((name, int(thr), want))
+        # the late key's set reads the late bytes, not K1's answers
+        self._late_track = None
+        if track_late is not None:
+            if int(track_late) < 1:
+                raise ValueError("a track threshold is at least 1")
+            name = b"hh:" + encode(late_key)
+            client.hh_create(name, late_key, capacity_log2)
+            self._late_track = (name, int(track_late), 1)
+        self._day_insight = day_profile is not None
+        self._profile = None
+        if day_profile is not None or late_key is not None:
+            self._profile = encode(day_profile) if day_profile is not None else b"tp:" + encode(late_key)
+            if self._profile not in client._tp:
+                client.tp_create(self._profile)
 
     def _buffers(self, n: int, width: int):
         b = self._bufs
@@ -73,28 +140,42 @@ class StudentCounts:
             ctx = self.client.ctx
             b = (cn, cw, DeviceBuffer(ctx, cn * cw + 64), DeviceBuffer(ctx, cn * 4 + 16),
                  DeviceBuffer(ctx, cn + 16))
+            if self._profile is not None:  # the times and the late bytes
+                b += (DeviceBuffer(ctx, cn * 8 + 16), DeviceBuffer(ctx, cn + 16))
             self._bufs = b
         return b[2:]
 
-    def update(self, bf_key, slots: np.ndarray, ids: np.ndarray) -> np.ndarray:
+    def update(self, bf_key, slots: np.ndarray, ids: np.ndarray, times=None) -> np.ndarray:
         """One batch of swipes: ``client.swipes_fixed`` semantics (BF.EXISTS
         of every id, PFADD of the valid ones into their HLL slot), then every
         valid swipe's id counts in the attended key and every invalid one's
         in the invalid key.  ``ids``: [n, width] uint8, ``slots``: one HLL
-        slot per swipe (``client.key_slot``).  Returns the validity (bool)."""
+        slot per swipe (``client.key_slot``).  ``times`` (one per swipe, any
+        form ``epoch_seconds`` takes; required with ``late_key`` or
+        ``day_profile``, refused without): every swipe counts in the profile,
+        every late one's id in the late key.  Returns the validity (bool)."""
         cl = self.client
         ids = np.ascontiguousarray(ids, dtype=np.uint8)
         if ids.ndim != 2:
             raise ValueError("ids must be a [n, width] uint8 array")
         n, width = ids.shape
+        if (times is None) != (self._profile is None):
+            raise ValueError("times go with late_key / day_profile: required with either, refused without")
+        ep = None
+        if times is not None:
+            ep = epoch_seconds(times)
+            if ep.size != n:
+                raise ValueError("one time per id")
         if n == 0 or width == 0:
             return np.zeros(n, bool)
         s = np.ascontiguousarray(slots, dtype=np.uint32)
         if s.shape != (n,):
             raise ValueError("one slot per id")
-        d_ids, d_slots, d_valid = self._buffers(n, width)
+        d_ids, d_slots, d_valid, *d_time = self._buffers(n, width)
         d_ids.from_host(ids)
         d_slots.from_host(s)
+        if ep is not None:
+            d_time[0].from_host(ep)
         bkey = encode(bf_key)
         if cl.keys.expect(bkey, "bf"):
             cl.ctx.call("ske_swipes_fixed", cl.keys.fid[bkey], C.c_void_p(d_slots.ptr), C.c_void_p(d_ids.ptr),
@@ -104,10 +185,23 @@ class StudentCounts:
         for key, want in ((self.attended_key, 1), (self.invalid_key, 0)):
             cl.ctx.call("ske_cms_add_fixed_async", cl.cms_cid(key), C.c_void_p(d_ids.ptr), width, n,
                         None, C.c_void_p(d_valid.ptr), want)
+        if ep is not None:  # every swipe into the profile; the late bytes mask the late key's add
+            d_epoch, d_late = d_time
+            late = self.late_key is not None
+            cl.ctx.call("ske_tp_add_async", cl.tp_tid(self._profile), C.c_void_p(d_epoch.ptr), n, None, 1,
+                        self.late_from, C.c_void_p(d_late.ptr) if late else None)
+            if late:
+                cl.ctx.call("ske_cms_add_fixed_async", cl.cms_cid(self.late_key), C.c_void_p(d_ids.ptr), width, n,
+                            None, C.c_void_p(d_late.ptr), 1)
         for name, thr, want in self._tracks:  # behind the adds: the estimates include this batch
             hid, cid = cl._hh_entry(name)
             cl.ctx.call("ske_hh_track_fixed_async", hid, cid, C.c_void_p(d_ids.ptr), width, n,
                         C.c_void_p(d_valid.ptr), want, thr)
+        if self._late_track is not None:
+            name, thr, want = self._late_track
+            hid, cid = cl._hh_entry(name)
+            cl.ctx.call("ske_hh_track_fixed_async", hid, cid, C.c_void_p(d_ids.ptr), width, n,
+                        C.c_void_p(d_time[1].ptr), want, thr)
         cl.ctx.call("ske_sync")
         return d_valid.to_host(np.uint8, n).astype(bool)
 
@@ -131,9 +225,9 @@ class StudentCounts:
 
     def _top(self, key, k, threshold):
         name = b"hh:" + encode(key)
-        track = [t for t in self._tracks if t[0] == name]
+        track = [t for t in self._tracks + [self._late_track] if t is not None and t[0] == name]
         if not track:
-            raise ValueError(f"{key} is not tracked (track_attended / track_invalid)")
+            raise ValueError(f"{key} is not tracked (track_attended / track_invalid / track_late)")
         thr = track[0][1] if threshold is None else int(threshold)
         if thr < track[0][1]:
             raise ValueError("a list threshold below the track threshold promises nothing")
@@ -154,14 +248,64 @@ class StudentCounts:
         """The same over the invalid attempts."""
         return self._top(self.invalid_key, k, threshold)
 
-    def insights(self, attended_threshold: int | None = None, invalid_threshold: int | None = None) -> list:
-        """The reference's two per-student insights (attendance_analysis.py:
-        105-118), ``data`` as ``{student_id: estimate}`` of the tracked keys.
+    def late(self, ids) -> np.ndarray:
+        """Estimated late swipes (valid or not) of each id."""
+        if self.late_key is None:
+            raise ValueError("no late_key")
+        return self._query(self.late_key, ids)
+
+    def top_late(self, k: int | None = None, threshold: int | None = None):
+        """The same over the late swipes (``track_late``)."""
+        if self.late_key is None:
+            raise ValueError("no late_key is tracked (track_late)")
+        return self._top(self.late_key, k, threshold)
+
+    def by_hour_of_week(self) -> np.ndarray:
+        """Swipes, valid or not, per weekday (Monday first) and UTC hour:
+        [7, 24] uint64."""
+        if self._profile is None:
+            raise ValueError("no time profile (late_key / day_profile)")
+        return self.client.tp_counts(self._profile)
+
+    def by_day(self) -> dict:
+        """``{day name: swipes}`` of the weekdays that have any, in the order of
+        the names, as pandas' ``groupby('day_of_week').size().to_dict()``
+        (attendance_analysis.py:78-84)."""
+        per_day = self.by_hour_of_week().sum(axis=1)
+        return {d: int(per_day[i]) for d, i in sorted((d, i) for i, d in enumerate(DAY_NAMES)) if per_day[i]}
+
+    def insights(self, attended_threshold: int | None = None, invalid_threshold: int | None = None,
+                 late_threshold: int | None = None) -> list:
+        """The reference's per-student and per-day insights (attendance_
+        analysis.py:65-85, :99-118) in its order, each only when its option is
+        on: "Habitual Latecomers" (``track_late``), "Attendance by Day"
+        (``day_profile``), then the two below.  ``data`` is ``{student_id:
+        estimate}`` of the tracked keys, ``{day name: swipes}`` by day.
         The reference picks its consistent attendees by the median plus the
         standard deviation of every student's count; a sketch holds no such
         population, so the caller passes the thresholds (default: the track
-        thresholds).  ``complete`` is added to each entry."""
+        thresholds).  ``complete`` is added to each per-student entry.
+
+        Latecomers with ``late_threshold=None`` follow the reference's rule
+        over what the set holds: listed at the track threshold, a student
+        stays whose estimate is above the median of the listed estimates --
+        the reference's result when ``track_late`` is 1, the list is complete
+        and the estimates are exact.  An integer works as the other two."""
         out = []
+        if self._late_track is not None:
+            ids, est, complete = self._top(self.late_key, None, late_threshold)
+            if late_threshold is None and len(ids):
+                keep = est > np.median(est)
+                ids, est = [i for i, k in zip(ids, keep) if k], est[keep]
+            out.append({"title": "Habitual Latecomers",
+                        "description": f"Found {len(ids)} students who frequently arrive after "
+                                       f"{self.late_from // 3600}:00 AM",
+                        "data": {i.decode("utf-8", "replace"): int(e) for i, e in zip(ids, est)},
+                        "complete": complete})
+        if self._day_insight:
+            out.append({"title": "Attendance by Day",
+                        "description": "Distribution of attendance across different days",
+                        "data": self.by_day()})
         for title, text, key, thr in (
                 ("Most Consistent Attendees", "Students whose estimated attendance reaches the threshold",
                  self.attended_key, attended_threshold),

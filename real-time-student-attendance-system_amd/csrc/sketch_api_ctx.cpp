@@ -1,7 +1,7 @@
 // sketch_api_ctx.cpp -- libsketch C-ABI (include/sketch.h): the context's
 // lifecycle, options, the sticky error word, streams, host -> device staging,
 // pass timing, the scratch-use ordering and graph capture.  The other
-// subsystems are sketch_api_{bloom,hll,swipes,ingest,cms,hh}.cpp (map: sketch_ctx.h).
+// subsystems are sketch_api_{bloom,hll,swipes,ingest,cms,hh,tp}.cpp (map: sketch_ctx.h).
 #include <stdlib.h>
 #include <string.h>
 
@@ -296,6 +296,8 @@ const char *ske_strerror(int code) {
     case SKE_EHHEXISTS: return "ERR heavy-hitter set already exists";
     case SKE_EHHCAP: return "ERR heavy-hitter capacity out of range";
     case SKE_EHHSPACE: return "ERR heavy-hitter list does not fit the output";
+    case SKE_ETPNOSET: return "ERR time profile does not exist";
+    case SKE_ETPEXISTS: return "ERR time profile already exists";
     default: return "ERR unknown";
     }
 }
@@ -337,6 +339,11 @@ int ske_open(int device, ske_ctx **out) {
         const unsigned long long cells = strtoull(v, nullptr, 10);
         c->hh_lds_cells = cells < kCmsLdsCells ? uint32_t(cells) : kCmsLdsCells;
     }
+    if (const char *v = getenv("SKE_TP_GRID")) {
+        const unsigned long long grid = strtoull(v, nullptr, 10);
+        c->tp_grid = int(grid < kTpMaxGrid ? grid : kTpMaxGrid);
+    }
+    if (const char *v = getenv("SKE_TP_FORM")) c->tp_form = strtoull(v, nullptr, 10) == 1 ? 1 : 0;
     if (hipMalloc(&c->zero16, 64) != hipSuccess || hipMemset(c->zero16, 0, 64) != hipSuccess) {
         ske_close(c);
         return SKE_ENOMEM;
@@ -352,6 +359,7 @@ int ske_close(ske_ctx *c) {
     for (auto &F : c->filters) free_filter(F);
     for (auto &T : c->cms) free_cms(T);
     for (auto &H : c->hh) free_hh(H);
+    for (auto &P : c->tp) free_tp(P);
     if (c->regs) (void)hipFree(c->regs);
     if (c->tau) (void)hipFree(c->tau);
     if (c->sig) (void)hipFree(c->sig);

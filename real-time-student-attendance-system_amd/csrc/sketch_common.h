@@ -383,4 +383,36 @@ SKE_HD bool gen_is_member(const GenDev &g, uint64_t x) {
     return (r * g.inv) % g.R < g.N;
 }
 
+// ---------------------------------------------------------------------------
+// Time profile (sketch_tp.hip): a swipe's time, seconds since 1970-01-01T00:00:00
+// UTC (any int64_t), as weekday (Monday = 0, datetime.weekday()), hour and
+// second of the day, all by floor division.  One 64-bit division by the constant
+// 86400 (a multiply-high), the rest in 32 bits:
+//   sod   the low words of epoch - day * 86400 decide it (its range is 17 bits);
+//   dow   (day + 3) mod 7, 1970-01-01 being a Thursday.  |day| < 1.07e14, so
+//         d = day + 3 + 7 * 2e13 is positive and below 2^48, and with
+//         2^32 = 4 and 2^16 = 2 (mod 7) its three 16-bit digits fold into one
+//         19-bit sum with the same remainder.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kTpBins = 168;  // weekday * 24 + hour (SKE_TP_BINS)
+struct TpTime {
+    uint32_t dow, hour, sod;
+};
+SKE_HD TpTime tp_time(int64_t epoch) {
+    int64_t day = epoch / 86400;  // toward zero; corrected to the floor below
+    int32_t sod = int32_t(uint32_t(uint64_t(epoch)) - uint32_t(uint64_t(day)) * 86400u);
+    if (sod < 0) {
+        sod += 86400;
+        day -= 1;
+    }
+    const uint64_t d = uint64_t(day + 3 + 140000000000000LL);
+    const uint32_t fold = uint32_t(d >> 32) * 4u + (uint32_t(d >> 16) & 0xffffu) * 2u + (uint32_t(d) & 0xffffu);
+    TpTime t;
+    t.dow = fold % 7u;
+    t.sod = uint32_t(sod);
+    t.hour = t.sod / 3600u;
+    return t;
+}
+SKE_HD uint32_t tp_bin(const TpTime &t) { return t.dow * 24u + t.hour; }
+
 }  // namespace ske

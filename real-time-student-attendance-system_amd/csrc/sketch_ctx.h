@@ -10,6 +10,7 @@
 //   sketch_api_ingest.cpp  ingest, the key table, the generator
 //   sketch_api_cms.cpp     Count-Min Sketch tables: init, add, query, merge, export / import
 //   sketch_api_hh.cpp      heavy-hitter sets beside a table: init, track, list
+//   sketch_api_tp.cpp      time profiles (weekday x hour counters): init, add, read / import
 // A helper used by one unit is static there; what crosses units is declared here.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -62,6 +63,11 @@ struct Hh {
     uint32_t log2 = 0;
 };
 
+// one time profile (counts == nullptr: the tid is free): kTpBins u64 counters
+struct Tp {
+    unsigned long long *counts = nullptr;  // device
+};
+
 struct Staged {
     const uint8_t *bytes = nullptr;
     const uint32_t *offs = nullptr;
@@ -94,6 +100,12 @@ struct ske_ctx {
     // a track copies tables up to this many cells into LDS (SKE_HH_LDS_CELLS,
     // read by ske_open, sets it for A/B timing, at most kCmsLdsCells; 0: never)
     uint32_t hh_lds_cells = ske::kHhLdsCells;
+    std::vector<ske::Tp> tp;    // by tid (sized on first use)
+    // workgroups of a time-profile add (SKE_TP_GRID, read by ske_open; 0: one
+    // per CU) and its form (SKE_TP_FORM: 0 a one-bin wavefront adds once, 1 per
+    // lane); for small-shape tests and A/B timing, neither changes a result
+    int tp_grid = 0;
+    int tp_form = 0;
     uint8_t *regs = nullptr;  // nslots * 16384
     uint32_t nslots = 0;
     double *tau = nullptr, *sig = nullptr;  // device estimator tables (lazy)
@@ -249,6 +261,9 @@ CmsTable table_of(const Cms &T);
 
 // ---- sketch_api_hh.cpp
 void free_hh(Hh &H);
+
+// ---- sketch_api_tp.cpp
+void free_tp(Tp &P);
 
 // ---- sketch_api_swipes.cpp
 bool use_lds(const ske_ctx *c, const ChainDev &ch);

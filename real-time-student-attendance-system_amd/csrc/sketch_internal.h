@@ -244,6 +244,20 @@ hipError_t launch_hh_track(const CmsTable &T, const CmsItems &I, const HhSet &S,
 hipError_t launch_hh_list(const CmsTable &T, const HhSet &S, uint32_t threshold, uint32_t cap, uint64_t *out_ids,
                           uint32_t *out_len, uint32_t *out_est, unsigned int *out_n, hipStream_t st);
 
+// sketch_tp.hip -- time profile: weekday x hour counters of a batch's swipe
+// times, and the per-swipe "late" byte
+struct TpArgs {
+    unsigned long long *counts;  // kTpBins counters
+    const int64_t *epoch;        // n seconds since 1970-01-01 UTC
+    const uint8_t *mask;         // nullptr: every swipe counts; else those with mask[i] == want
+    uint8_t *late;               // nullptr, or n bytes: second of the day >= late_from
+    uint32_t n, want, late_from;
+};
+constexpr unsigned kTpMaxGrid = 4096;
+// form 0: a wavefront whose tile falls into one bin adds it as one LDS atomic;
+// 1: one LDS atomic per lane, always.  grid: workgroups (at most kTpMaxGrid; fewer for a small n)
+hipError_t launch_tp_add(const TpArgs &A, int form, unsigned grid, hipStream_t st);
+
 // sketch_order.hip -- order-exact paths (replies that depend on item order)
 struct Scratch;  // growable device scratch, owned by the context
 constexpr int kScratchSlots = 48;

@@ -13,7 +13,7 @@ import gc
 
 import numpy as np
 
-from ._lib import CmsInfo, Context, GenParams, HhInfo, SKE_HH_ID_BYTES, SKE_MEM_DEVICE
+from ._lib import CmsInfo, Context, GenParams, HhInfo, SKE_HH_ID_BYTES, SKE_MEM_DEVICE, SKE_TP_BINS
 from . import synthetic
 
 PASS_KINDS = 9  # SKE_PASS_KINDS (include/sketch.h)
@@ -86,6 +86,22 @@ def hh_list(ctx: Context, hid: int, cid: int, threshold: int, room: int | None =
              lens.ctypes.data_as(C.c_void_p), est.ctypes.data_as(C.c_void_p), room, C.byref(n), C.byref(complete))
     k = int(n.value)
     return [ids[i, :lens[i]].tobytes() for i in range(k)], est[:k].copy(), bool(complete.value)
+
+
+def tp_counts(ctx: Context, tid: int) -> np.ndarray:
+    """ske_tp_read: the profile's counters as [7, 24] uint64 (weekday, Monday
+    first, by hour)."""
+    out = np.zeros(SKE_TP_BINS, np.uint64)
+    ctx.call("ske_tp_read", int(tid), out.ctypes.data_as(C.c_void_p))
+    return out.reshape(7, 24)
+
+
+def tp_import(ctx: Context, tid: int, counts) -> None:
+    """ske_tp_import: overwrite the profile's counters (168 values, any shape)."""
+    a = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    if a.size != SKE_TP_BINS:
+        raise ValueError(f"a time profile has {SKE_TP_BINS} counters")
+    ctx.call("ske_tp_import", int(tid), a.ctypes.data_as(C.c_void_p))
 
 
 class SweBatch(C.Structure):
@@ -361,6 +377,34 @@ class SketchEngine:
 
     def hh_list(self, hid: int, cid: int, threshold: int):
         return hh_list(self.ctx, hid, cid, threshold)
+
+    # ---- time profile: weekday x hour counters of the swipes' times
+    def tp_init(self, tid: int):
+        self.ctx.call("ske_tp_init", int(tid))
+
+    def tp_free(self, tid: int):
+        self.ctx.call("ske_tp_free", int(tid))
+
+    def tp_reset(self, tid: int):
+        self.ctx.call("ske_tp_reset", int(tid))
+
+    def tp_counts(self, tid: int) -> np.ndarray:
+        return tp_counts(self.ctx, tid)
+
+    def tp_import(self, tid: int, counts):
+        tp_import(self.ctx, tid, counts)
+
+    def tp_add(self, tid: int, epoch: DeviceBuffer, n: int, mask: DeviceBuffer | None = None, want: int = 1,
+               late_from: int = 32400, late: DeviceBuffer | None = None):
+        """One resident batch of ``n`` swipe times (int64 seconds since
+        1970-01-01 UTC) into profile ``tid``: with ``mask`` only the swipes
+        whose mask byte equals ``want`` count.  ``late`` (n bytes) receives 1
+        for every swipe, masked or not, whose second of the day is at least
+        ``late_from``.  Only enqueued (ske_tp_add_async, capturable; ``sync()``
+        waits)."""
+        self.ctx.call("ske_tp_add_async", int(tid), C.c_void_p(epoch.ptr), int(n),
+                      C.c_void_p(mask.ptr) if mask else None, int(want), int(late_from),
+                      C.c_void_p(late.ptr) if late else None)
 
     # ---- HIP graphs: record enqueue-only calls once, replay many times
     def capture(self, fn) -> "Graph":
