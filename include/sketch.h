@@ -276,6 +276,14 @@ int ske_cms_incrby(ske_ctx *ctx, uint32_t cid, const uint8_t *bytes, const uint3
 int ske_cms_add_fixed_async(ske_ctx *ctx, uint32_t cid, const uint8_t *ids, uint32_t width,
                             uint64_t n, const uint32_t *incr_or_null, const uint8_t *mask_or_null,
                             int want);
+/* The same over packed ids on the device (id i = bytes[offs[i] .. offs[i + 1]),
+ * offs n + 1 entries; bytes readable to the next 8-byte boundary behind the
+ * last id), enqueue only and graph-capturable: the form that follows
+ * ske_ingest_dense.  An empty id counts as the empty string, as in
+ * ske_cms_incrby. */
+int ske_cms_add_packed_async(ske_ctx *ctx, uint32_t cid, const uint8_t *bytes_dev, const uint32_t *offs_dev,
+                             uint64_t n, const uint32_t *incr_or_null, const uint8_t *mask_or_null,
+                             int want);
 /* CMS.QUERY key item...: out[i] = the minimum of item i's cells */
 int ske_cms_query(ske_ctx *ctx, uint32_t cid, const uint8_t *bytes, const uint32_t *offs,
                   uint64_t n, uint32_t *out, int mem);
@@ -337,6 +345,15 @@ int ske_hh_info(ske_ctx *ctx, uint32_t hid, ske_hh_info_t *out);
  * cid at every call). */
 int ske_hh_track_fixed_async(ske_ctx *ctx, uint32_t hid, uint32_t cid, const uint8_t *ids, uint32_t width,
                              uint64_t n, const uint8_t *mask_or_null, int want, uint32_t threshold);
+/* The same over packed ids on the device (bytes + offs[n + 1], as
+ * ske_cms_add_packed_async), enqueue only and graph-capturable.  It has no
+ * wait and so no error of its own for an id longer than SKE_HH_ID_BYTES: the
+ * id is skipped and the set's sticky overflow word is set, so listings answer
+ * complete = 0 ("may miss students") until ske_hh_reset.  An empty id is
+ * tracked as the empty string, as in ske_hh_track. */
+int ske_hh_track_packed_async(ske_ctx *ctx, uint32_t hid, uint32_t cid, const uint8_t *bytes_dev,
+                              const uint32_t *offs_dev, uint64_t n, const uint8_t *mask_or_null, int want,
+                              uint32_t threshold);
 /* The packed form (bytes + offs[n + 1]); returns when done.  An id longer than
  * SKE_HH_ID_BYTES fails the call with SKE_ETOOLONG: with SKE_MEM_HOST before
  * anything is tracked, with SKE_MEM_DEVICE after the batch's other ids were. */
@@ -553,11 +570,43 @@ int ske_ingest_swipes(ske_ctx *ctx, uint32_t fid, const uint8_t *msgs,
                       const ske_ingest_cols_t *cols, uint64_t n, uint8_t *valid_dev,
                       uint64_t *ntaken);
 
+/* The decoded messages' times: epoch_dev[i] (8-byte aligned, n entries) = the
+ * timestamp span of message i as seconds since 1970-01-01T00:00:00 UTC when
+ * status[i] == 0, else 0 -- analysis.epoch_seconds(datetime.fromisoformat(text)):
+ * a naive timestamp is UTC as written, an offset is subtracted, a date-only
+ * form is midnight, a fraction is dropped (the floor, also before 1970).  The
+ * span was validated by ske_ingest_parse and is decoded by position; at most
+ * five aligned 8-byte words of it are read.  Enqueue only. */
+int ske_ingest_times(ske_ctx *ctx, const uint8_t *msgs, const ske_ingest_cols_t *cols, uint64_t n,
+                     int64_t *epoch_dev);
+/* The decoded messages (status 0), in message order, as one packed batch on the
+ * device -- the input of ske_cms_add_packed_async / ske_hh_track_packed_async /
+ * ske_tp_add_async.  All pointers are device pointers owned by the caller:
+ * ids cap_bytes bytes and readable to the next 8-byte boundary, offs n + 1
+ * entries, epoch (8-byte aligned), valid and at n entries.  Entry r of the
+ * *ndense decoded messages: its id bytes at ids[offs[r] .. offs[r + 1]), its
+ * epoch (epoch_dev of its message; 0 when that is NULL), its BF.EXISTS byte
+ * (valid_dev of its message; 0 when NULL) and its message index at[r].
+ * *nbytes = offs[*ndense].  More than cap_bytes: SKE_EINVAL with both totals
+ * set and nothing written.  Waits for the stream (it returns the totals), so
+ * it cannot be recorded: SKE_EBUSY. */
+typedef struct {
+    uint8_t *ids;
+    uint32_t *offs;
+    int64_t *epoch;
+    uint8_t *valid;
+    uint32_t *at;
+} ske_ingest_dense_t;
+int ske_ingest_dense(ske_ctx *ctx, const uint8_t *msgs, const ske_ingest_cols_t *cols, uint64_t n,
+                     const uint8_t *valid_dev_or_null, const int64_t *epoch_dev_or_null,
+                     const ske_ingest_dense_t *out, uint64_t cap_bytes, uint64_t *ndense, uint64_t *nbytes);
+
 /* ---- stream capture (HIP graphs) ----
  * Record the device work of the calls made between begin and end on the
  * context stream (only enqueue-only calls: ske_swipes_async,
- * ske_swipes_fixed_async, ske_cms_add_fixed_async, ske_hh_track_fixed_async,
- * ske_tp_add_async) into an executable graph, uploaded to the device;
+ * ske_swipes_fixed_async, ske_cms_add_fixed_async, ske_cms_add_packed_async,
+ * ske_hh_track_fixed_async, ske_hh_track_packed_async, ske_tp_add_async,
+ * ske_ingest_times) into an executable graph, uploaded to the device;
  * each ske_graph_launch replays it on the context stream.  A consumer that
  * processes a ring of fixed device batch slots replays one graph per turn of
  * the ring instead of one launch per batch (SURVEY.md §8a-1's processor loop at

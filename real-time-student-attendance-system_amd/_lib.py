@@ -96,6 +96,12 @@ class IngestCols(C.Structure):
                 ("ts_len", C.c_void_p), ("day", C.c_void_p), ("kh", C.c_void_p)]
 
 
+class IngestDense(C.Structure):
+    """ske_ingest_dense_t (include/sketch.h)."""
+    _fields_ = [("ids", C.c_void_p), ("offs", C.c_void_p), ("epoch", C.c_void_p), ("valid", C.c_void_p),
+                ("at", C.c_void_p)]
+
+
 class GenParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("id_lo", C.c_uint64), ("id_hi", C.c_uint64),
                 ("n_members", C.c_uint64), ("perm_mul", C.c_uint64), ("perm_add", C.c_uint64),
@@ -156,6 +162,7 @@ SIGNATURES = {
     "ske_cms_incrby": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, C.c_uint64, _u32p, _u32p, C.c_int]),
     "ske_cms_add_fixed_async": (C.c_int, [_CTX, C.c_uint32, _u8p, C.c_uint32, C.c_uint64, _u32p, _u8p,
                                           C.c_int]),
+    "ske_cms_add_packed_async": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, C.c_uint64, _u32p, _u8p, C.c_int]),
     "ske_cms_query": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, C.c_uint64, _u32p, C.c_int]),
     "ske_cms_merge": (C.c_int, [_CTX, C.c_uint32, _u32p, _vp, C.c_uint32]),
     "ske_cms_export": (C.c_int, [_CTX, C.c_uint32, _u32p, C.c_uint64]),
@@ -166,6 +173,8 @@ SIGNATURES = {
     "ske_hh_info": (C.c_int, [_CTX, C.c_uint32, C.POINTER(HhInfo)]),
     "ske_hh_track_fixed_async": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, _u8p, C.c_uint32, C.c_uint64, _u8p,
                                            C.c_int, C.c_uint32]),
+    "ske_hh_track_packed_async": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, _u8p, _u32p, C.c_uint64, _u8p,
+                                            C.c_int, C.c_uint32]),
     "ske_hh_track": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, _u8p, _u32p, C.c_uint64, C.c_uint32, C.c_int]),
     "ske_hh_list": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_uint32, _u8p, _u32p, _u32p, C.c_uint64,
                               C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
@@ -201,6 +210,10 @@ SIGNATURES = {
     "ske_keytab_clear": (C.c_int, [_CTX]),
     "ske_ingest_swipes": (C.c_int, [_CTX, C.c_uint32, _u8p, C.POINTER(IngestCols), C.c_uint64, _u8p,
                                     C.POINTER(C.c_uint64)]),
+    "ske_ingest_times": (C.c_int, [_CTX, _u8p, C.POINTER(IngestCols), C.c_uint64, _vp]),
+    "ske_ingest_dense": (C.c_int, [_CTX, _u8p, C.POINTER(IngestCols), C.c_uint64, _u8p, _vp,
+                                   C.POINTER(IngestDense), C.c_uint64, C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_uint64)]),
     "ske_capture_begin": (C.c_int, [_CTX]),
     "ske_capture_end": (C.c_int, [_CTX, C.POINTER(C.c_void_p)]),
     "ske_graph_launch": (C.c_int, [_CTX, _vp]),

@@ -22,6 +22,12 @@ swipe's time.  With ``late_key`` / ``day_profile`` set, ``update`` takes the
 times too: a time profile (client_tp.py, DESIGN.md "Time profile") counts the
 swipes per weekday and hour and marks the late ones on the device, and that
 mark is the mask of a third Count-Min key, the late swipes per student.
+
+The reference has none of this as arrays; it has JSON messages.
+``update_messages`` takes those: the device decodes them (client_ingest.py),
+timestamps included, and the decoded ids, answers and times feed the same
+counters in place (DESIGN.md "Insights from the message stream");
+``count_packed`` is the counting alone, for swipes already answered.
 """
 from __future__ import annotations
 
@@ -30,7 +36,8 @@ from datetime import datetime, timedelta, timezone
 
 import numpy as np
 
-from ._lib import SKE_MEM_DEVICE
+from ._lib import IngestDense, SKE_MEM_DEVICE
+from .client_ingest import join_messages
 from .encoding import encode, pack
 from .engine import DeviceBuffer
 
@@ -105,6 +112,7 @@ class StudentCounts:
                 client.cms_initbyprob(key, error, probability)
             client.keys.expect(encode(key), "cms")  # WRONGTYPE for a key of another kind
         self._bufs = None
+        self._pk_bufs: dict[str, dict] = {}  # _packed_buffers
         # per key: (set name, track threshold, the mask value its swipes carry)
         self._tracks = []
         for key, thr, want in ((attended_key, track_attended, 1), (invalid_key, track_invalid, 0)):
@@ -204,6 +212,138 @@ class StudentCounts:
                         C.c_void_p(d_time[1].ptr), want, thr)
         cl.ctx.call("ske_sync")
         return d_valid.to_host(np.uint8, n).astype(bool)
+
+    @property
+    def timed(self) -> bool:
+        """Whether the counting calls take the swipes' times (``late_key`` /
+        ``day_profile``)."""
+        return self._profile is not None
+
+    def _enqueue_packed(self, d_ids, d_offs, n: int, d_valid, d_epoch, d_late) -> None:
+        """The counting half of ``update`` over a packed batch on the device
+        (id i = ``ids[offs[i]:offs[i + 1]]``), enqueued in ``update``'s order:
+        the attended and invalid adds masked by the valid bytes; with the time
+        options the profile add, which writes the late bytes, and the late
+        key's add masked by them; then the tracks."""
+        cl = self.client
+        ids, offs, valid = C.c_void_p(d_ids.ptr), C.c_void_p(d_offs.ptr), C.c_void_p(d_valid.ptr)
+        for key, want in ((self.attended_key, 1), (self.invalid_key, 0)):
+            cl.ctx.call("ske_cms_add_packed_async", cl.cms_cid(key), ids, offs, n, None, valid, want)
+        if d_epoch is not None:
+            late = self.late_key is not None
+            cl.ctx.call("ske_tp_add_async", cl.tp_tid(self._profile), C.c_void_p(d_epoch.ptr), n, None, 1,
+                        self.late_from, C.c_void_p(d_late.ptr) if late else None)
+            if late:
+                cl.ctx.call("ske_cms_add_packed_async", cl.cms_cid(self.late_key), ids, offs, n, None,
+                            C.c_void_p(d_late.ptr), 1)
+        for name, thr, want in self._tracks:
+            hid, cid = cl._hh_entry(name)
+            cl.ctx.call("ske_hh_track_packed_async", hid, cid, ids, offs, n, valid, want, thr)
+        if self._late_track is not None:
+            name, thr, want = self._late_track
+            hid, cid = cl._hh_entry(name)
+            cl.ctx.call("ske_hh_track_packed_async", hid, cid, ids, offs, n, C.c_void_p(d_late.ptr), want, thr)
+
+    def _packed_buffers(self, which: str, n: int, nbytes: int) -> dict:
+        """Device buffers of a packed batch of up to ``n`` ids in ``nbytes``
+        bytes, kept between calls (``which``: "host", ``count_packed``'s
+        upload, or "dense", ``update_messages``' batch)."""
+        b = self._pk_bufs.get(which)
+        if b is None or b["n"] < n or b["nbytes"] < nbytes:
+            if b is not None:
+                for x in b.values():
+                    if isinstance(x, DeviceBuffer):
+                        x.free()
+            cn, cb = max(n, 1024), max(nbytes, 1 << 14)
+            ctx = self.client.ctx
+            b = {"n": cn, "nbytes": cb, "ids": DeviceBuffer(ctx, cb + 64), "offs": DeviceBuffer(ctx, (cn + 1) * 4),
+                 "valid": DeviceBuffer(ctx, cn + 16)}
+            if self.timed or which == "dense":
+                b["epoch"] = DeviceBuffer(ctx, cn * 8 + 16)
+                b["late"] = DeviceBuffer(ctx, cn + 16)
+            if which == "dense":  # every message's epoch before compaction; the entries' message indices
+                b["epoch_all"] = DeviceBuffer(ctx, cn * 8 + 16)
+                b["at"] = DeviceBuffer(ctx, cn * 4 + 16)
+            self._pk_bufs[which] = b
+        return b
+
+    def _check_times(self, times, n: int):
+        if (times is None) != (self._profile is None):
+            raise ValueError("times go with late_key / day_profile: required with either, refused without")
+        if times is None:
+            return None
+        ep = epoch_seconds(times)
+        if ep.size != n:
+            raise ValueError("one time per id")
+        return ep
+
+    def count_packed(self, buf, offs, valid, times=None) -> None:
+        """The counting half of ``update`` for swipes whose BF.EXISTS answers
+        the caller already has: id i is ``buf[offs[i]:offs[i + 1]]`` (the ids
+        as redis-py encodes them, ``encoding.pack``), ``valid`` one answer per
+        id.  Every valid swipe's id counts in the attended key and every
+        invalid one's in the invalid key; ``times`` as in ``update``.  No
+        swipe call is made.  Uploads, enqueues, returns when done."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+        offs = np.ascontiguousarray(offs, dtype=np.uint32).reshape(-1)
+        n = offs.size - 1
+        v = np.ascontiguousarray(np.asarray(valid).astype(bool), dtype=np.uint8).reshape(-1)
+        if n < 0 or v.size != n:
+            raise ValueError("one valid answer per id, offs one entry more")
+        ep = self._check_times(times, n)
+        if n == 0:
+            return
+        b = self._packed_buffers("host", n, int(offs[-1]))
+        b["ids"].from_host(buf[:int(offs[-1])])
+        b["offs"].from_host(offs)
+        b["valid"].from_host(v)
+        if ep is not None:
+            b["epoch"].from_host(ep)
+        self._enqueue_packed(b["ids"], b["offs"], n, b["valid"], b["epoch"] if ep is not None else None,
+                             b.get("late"))
+        self.client.ctx.call("ske_sync")
+
+    def update_messages(self, bf_key, messages, hll_key_prefix: str = "hll:unique:", key_form: str = "readme"):
+        """``client.ingest`` over raw message payloads, and every decodable
+        message's swipe counted as ``update`` counts it: its student id in the
+        attended or the invalid key by its BF.EXISTS answer and, with the time
+        options, its ``timestamp`` -- as ``epoch_seconds(fromisoformat(...))``
+        -- in the profile and, when late, its id in the late key.  Messages
+        decoded on the device are counted there: their ids, answers and times
+        never come to the host.  The others are decoded by Python, as
+        ``ingest`` does, and counted through ``count_packed``; a message that
+        cannot be decoded (status -1) counts nowhere.  Returns ``(valid,
+        status)`` as ``ingest``."""
+        blob, moffs = join_messages(messages)
+        return self.update_messages_packed(bf_key, blob, moffs, hll_key_prefix, key_form)
+
+    def update_messages_packed(self, bf_key, blob, moffs, hll_key_prefix: str = "hll:unique:",
+                               key_form: str = "readme"):
+        """``update_messages`` over payloads already laid end to end
+        (``client.ingest_packed``'s layout)."""
+        cl = self.client
+        valid, status, run = cl._ingest_batch(bf_key, blob, moffs, hll_key_prefix, key_form)
+        if run is None:
+            return valid, status
+        B, n = run.B, run.n
+        d = self._packed_buffers("dense", n, B["msgs"].nbytes)  # an id is a piece of its message
+        msgs = C.c_void_p(B["msgs"].ptr)
+        if self.timed:
+            cl.ctx.call("ske_ingest_times", msgs, C.byref(run.cols), n, C.c_void_p(d["epoch_all"].ptr))
+        out = IngestDense(*[C.c_void_p(d[k].ptr) for k in ("ids", "offs", "epoch", "valid", "at")])
+        ndense, nbytes = C.c_uint64(), C.c_uint64()
+        cl.ctx.call("ske_ingest_dense", msgs, C.byref(run.cols), n,
+                    C.c_void_p(B["valid"].ptr) if run.has_bf else None,  # a missing key answers 0
+                    C.c_void_p(d["epoch_all"].ptr) if self.timed else None, C.byref(out), d["nbytes"],
+                    C.byref(ndense), C.byref(nbytes))
+        if ndense.value:
+            self._enqueue_packed(d["ids"], d["offs"], int(ndense.value), d["valid"],
+                                 d["epoch"] if self.timed else None, d["late"])
+            cl.ctx.call("ske_sync")
+        if run.host_at:
+            hbuf, hoffs = pack(run.host_ids)
+            self.count_packed(hbuf, hoffs, valid[np.asarray(run.host_at)], run.host_ts if self.timed else None)
+        return valid, status
 
     def _query(self, key, ids) -> np.ndarray:
         if isinstance(ids, np.ndarray) and ids.dtype == np.uint8 and ids.ndim == 2:

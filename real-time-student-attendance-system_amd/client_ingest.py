@@ -42,8 +42,37 @@ class IngestState:
         return self.bufs
 
 
+class IngestRun:
+    """What one ``_ingest_batch`` leaves for a caller that goes on with the
+    batch on the device (``StudentCounts.update_messages``): the device
+    buffers and parse columns, whether BF.EXISTS ran (``B["valid"]`` holds the
+    answers), and the host-decoded messages -- their indices, encoded ids and
+    timestamps."""
+
+    def __init__(self, B, cols, n, has_bf, host_at, host_ids, host_ts):
+        self.B, self.cols, self.n, self.has_bf = B, cols, n, has_bf
+        self.host_at, self.host_ids, self.host_ts = host_at, host_ids, host_ts
+
+
 def _message(blob: memoryview, moffs: np.ndarray, i) -> bytes:
     return blob[moffs[i]:moffs[i + 1]].tobytes()
+
+
+def join_messages(messages: Sequence) -> tuple[np.ndarray, np.ndarray]:
+    """Message payloads laid end to end: ``(blob, moffs)``, message i is
+    ``blob[moffs[i]:moffs[i+1]]``."""
+    n = len(messages)
+    try:
+        joined = b"".join(messages)
+        raw = messages
+    except TypeError:  # str payloads: as .decode() would see them
+        raw = [m if isinstance(m, (bytes, bytearray, memoryview)) else str(m).encode()
+               for m in messages]
+        joined = b"".join(raw)
+    lens = np.fromiter(map(len, raw), np.uint32, count=n)
+    moffs = np.zeros(n + 1, np.uint32)
+    np.cumsum(lens, out=moffs[1:])
+    return np.frombuffer(joined, np.uint8), moffs
 
 
 class IngestMixin:
@@ -61,41 +90,35 @@ class IngestMixin:
         ``(valid, status)``: per message the BF.EXISTS answer and 0 decoded on
         the device, 1 decoded on the host, -1 not decodable (the reference's
         negative_acknowledge, :134-136)."""
-        n = len(messages)
-        try:
-            joined = b"".join(messages)
-            raw = messages
-        except TypeError:  # str payloads: as .decode() would see them
-            raw = [m if isinstance(m, (bytes, bytearray, memoryview)) else str(m).encode()
-                   for m in messages]
-            joined = b"".join(raw)
-        lens = np.fromiter(map(len, raw), np.uint32, count=n)
-        moffs = np.zeros(n + 1, np.uint32)
-        np.cumsum(lens, out=moffs[1:])
-        return self.ingest_packed(bf_key, np.frombuffer(joined, np.uint8), moffs, hll_key_prefix,
-                                  key_form)
+        blob, moffs = join_messages(messages)
+        return self.ingest_packed(bf_key, blob, moffs, hll_key_prefix, key_form)
 
     def ingest_packed(self, bf_key, blob: np.ndarray, moffs: np.ndarray,
                       hll_key_prefix: str = "hll:unique:", key_form: str = "readme"):
         """``ingest`` over payloads already laid end to end: message i is
         ``blob[moffs[i]:moffs[i+1]]`` (the layout a network consumer fills)."""
+        return self._ingest_batch(bf_key, blob, moffs, hll_key_prefix, key_form)[:2]
+
+    def _ingest_batch(self, bf_key, blob, moffs, hll_key_prefix, key_form):
+        """``ingest_packed``'s work; returns ``(valid, status, run)`` with
+        ``run`` an ``IngestRun`` (None for an empty batch)."""
         blob = np.ascontiguousarray(blob, np.uint8)
         moffs = np.ascontiguousarray(moffs, np.uint32)
         n = len(moffs) - 1
         valid = np.zeros(n, bool)
         status = np.zeros(n, np.int8)
         if n <= 0:
-            return valid, status
+            return valid, status, None
         day_form = 1 if key_form == "readme" else 0
         prefix = str(hll_key_prefix)
         mv = memoryview(blob)
 
-        def key_name(i) -> tuple[dict, bytes]:
-            """Message i decoded as Python does, and its HLL key."""
+        def key_name(i) -> tuple[dict, bytes, datetime]:
+            """Message i decoded as Python does, its HLL key and its time."""
             data = json.loads(_message(mv, moffs, i).decode())
             lecture_id = data["lecture_id"]
             ts = datetime.fromisoformat(data["timestamp"])
-            return data, encode(day_key(prefix, lecture_id, None if key_form == "code" else ts))
+            return data, encode(day_key(prefix, lecture_id, None if key_form == "code" else ts)), ts
 
         if self._ingest is None:
             self._ingest = IngestState(self.ctx)
@@ -109,10 +132,10 @@ class IngestMixin:
             self.ctx.call("ske_ingest_swipes", self.keys.fid[bkey], C.c_void_p(B["msgs"].ptr),
                           C.byref(cols), n, C.c_void_p(B["valid"].ptr), C.byref(taken))
             valid[:] = B["valid"].to_host(np.uint8, n).astype(bool)
-        keys, at = self._ingest_host_path(bkey, np.nonzero(dev_status != 0)[0], key_name, valid, status)
+        keys, at, ids, tss = self._ingest_host_path(bkey, np.nonzero(dev_status != 0)[0], key_name, valid, status)
         if tentative:
             self._ingest_release_unused(B, cols, n, tentative, has_bf, valid, dev_status, keys, at)
-        return valid, status
+        return valid, status, IngestRun(B, cols, n, has_bf, at, ids, tss)
 
     def _ingest_parse(self, B, blob, moffs, n, day_form) -> IngestCols:
         """Upload the payloads and decode them on the device."""
@@ -157,11 +180,11 @@ class IngestMixin:
     def _ingest_host_path(self, bkey, host, key_name, valid, status):
         """The messages the device did not decode: Python's json / datetime
         semantics, then ``swipes``.  Fills their ``valid`` / ``status``; returns
-        their keys and message indices."""
-        ids, keys, at = [], [], []
+        their keys, message indices, encoded ids and times."""
+        ids, keys, at, tss = [], [], [], []
         for m in host:
             try:
-                data, name = key_name(m)
+                data, name, ts = key_name(m)
                 sid = encode(data["student_id"])
             except Exception:
                 status[m] = -1
@@ -170,9 +193,10 @@ class IngestMixin:
             ids.append(sid)
             keys.append(name)
             at.append(m)
+            tss.append(ts)
         if at:
             valid[np.asarray(at)] = self.swipes(bkey, keys, ids)
-        return keys, at
+        return keys, at, ids, tss
 
     def _ingest_release_unused(self, B, cols, n, tentative, has_bf, valid, dev_status, keys, at):
         """Keys created for this batch that no valid swipe reached are not

@@ -161,6 +161,24 @@ int ske_cms_add_fixed_async(ske_ctx *c, uint32_t cid, const uint8_t *ids, uint32
     return SKE_OK;
 }
 
+int ske_cms_add_packed_async(ske_ctx *c, uint32_t cid, const uint8_t *bytes, const uint32_t *offs, uint64_t n,
+                             const uint32_t *incr, const uint8_t *mask, int want) {
+    if (!c) return SKE_EINVAL;
+    Cms *T = get_cms(c, cid);
+    if (!T) return SKE_ECMSNOKEY;
+    if (n == 0) return SKE_OK;
+    if (!bytes || !offs || n >= 0xffffffffull || (want != 0 && want != 1)) return SKE_EINVAL;
+    CmsItems I{};
+    I.bytes = bytes;
+    I.offs = offs;
+    I.n = uint32_t(n);
+    I.incr = incr;
+    I.mask = mask;
+    I.want = uint32_t(want);
+    HIPCHK(c, launch_cms_add(table_of(*T), I, cms_use_lds(c, *T), c->cus, c->st));
+    return SKE_OK;
+}
+
 int ske_cms_query(ske_ctx *c, uint32_t cid, const uint8_t *bytes, const uint32_t *offs, uint64_t n,
                   uint32_t *out, int mem) {
     if (!c) return SKE_EINVAL;

@@ -343,6 +343,10 @@ int ske_open(int device, ske_ctx **out) {
         const unsigned long long grid = strtoull(v, nullptr, 10);
         c->tp_grid = int(grid < kTpMaxGrid ? grid : kTpMaxGrid);
     }
+    if (const char *v = getenv("SKE_INGEST_GRID")) {
+        const unsigned long long grid = strtoull(v, nullptr, 10);
+        c->ingest_grid = int(grid < 65536 ? grid : 65536);
+    }
     if (const char *v = getenv("SKE_TP_FORM")) c->tp_form = strtoull(v, nullptr, 10) == 1 ? 1 : 0;
     if (hipMalloc(&c->zero16, 64) != hipSuccess || hipMemset(c->zero16, 0, 64) != hipSuccess) {
         ske_close(c);

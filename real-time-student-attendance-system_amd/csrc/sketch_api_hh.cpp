@@ -130,6 +130,29 @@ int ske_hh_track_fixed_async(ske_ctx *c, uint32_t hid, uint32_t cid, const uint8
     return SKE_OK;
 }
 
+int ske_hh_track_packed_async(ske_ctx *c, uint32_t hid, uint32_t cid, const uint8_t *bytes, const uint32_t *offs,
+                              uint64_t n, const uint8_t *mask, int want, uint32_t threshold) {
+    if (!c) return SKE_EINVAL;
+    Hh *H = get_hh(c, hid);
+    if (!H) return SKE_EHHNOSET;
+    Cms *T = get_cms(c, cid);
+    if (!T) return SKE_ECMSNOKEY;
+    if (threshold == 0 || (want != 0 && want != 1) || n >= 0xffffffffull) return SKE_EINVAL;
+    if (n == 0) return SKE_OK;
+    if (!bytes || !offs) return SKE_EINVAL;
+    CmsItems I{};
+    I.bytes = bytes;
+    I.offs = offs;
+    I.n = uint32_t(n);
+    I.mask = mask;
+    I.want = uint32_t(want);
+    // an id longer than SKE_HH_ID_BYTES is skipped and is a refused insert: the
+    // kernel's too-long word is the set's sticky overflow word
+    const HhSet S = set_of(*H);
+    HIPCHK(c, launch_hh_track(table_of(*T), I, S, threshold, hh_use_lds(c, *T), S.overflow, c->cus, c->st));
+    return SKE_OK;
+}
+
 int ske_hh_track(ske_ctx *c, uint32_t hid, uint32_t cid, const uint8_t *bytes, const uint32_t *offs, uint64_t n,
                  uint32_t threshold, int mem) {
     if (!c) return SKE_EINVAL;

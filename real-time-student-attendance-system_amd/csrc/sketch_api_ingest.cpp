@@ -208,6 +208,50 @@ int ske_ingest_swipes(ske_ctx *c, uint32_t fid, const uint8_t *msgs, const ske_i
     return check_call_err(c);
 }
 
+int ske_ingest_times(ske_ctx *c, const uint8_t *msgs, const ske_ingest_cols_t *cols, uint64_t n,
+                     int64_t *epoch_dev) {
+    if (!c || !cols || (n && (!msgs || !epoch_dev))) return SKE_EINVAL;
+    if (reinterpret_cast<uintptr_t>(epoch_dev) & 7) return SKE_EINVAL;
+    HIPCHK(c, launch_ingest_times(msgs, ingest_cols(cols), n, epoch_dev, c->cus, unsigned(c->ingest_grid), c->st));
+    return SKE_OK;
+}
+
+int ske_ingest_dense(ske_ctx *c, const uint8_t *msgs, const ske_ingest_cols_t *cols, uint64_t n,
+                     const uint8_t *valid_dev, const int64_t *epoch_dev, const ske_ingest_dense_t *out,
+                     uint64_t cap_bytes, uint64_t *ndense, uint64_t *nbytes) {
+    if (!c || !cols || !out || !ndense || !nbytes) return SKE_EINVAL;
+    *ndense = *nbytes = 0;
+    if (!n) return SKE_OK;
+    if (!msgs || !out->ids || !out->offs || !out->epoch || !out->valid || !out->at) return SKE_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(out->epoch) & 7) || n >= (uint64_t(1) << 31)) return SKE_EINVAL;
+    if (c->capturing) {
+        c->last_hip = "ske_ingest_dense waits for the stream and cannot be recorded";
+        return SKE_EBUSY;
+    }
+    hipError_t e = hipSuccess;
+    uint32_t *flag = (uint32_t *)scratch_get(c->scratch, kScrKtFlag, n * 4, &e);
+    uint32_t *mlen = (uint32_t *)scratch_get(c->scratch, kScrKtLen, n * 4, &e);
+    uint32_t *flag_incl = (uint32_t *)scratch_get(c->scratch, kScrInFlagIncl, n * 4, &e);
+    uint32_t *len_incl = (uint32_t *)scratch_get(c->scratch, kScrInLenIncl, n * 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    const IngestCols k = ingest_cols(cols);
+    const unsigned grid = unsigned(c->ingest_grid);
+    HIPCHK(c, launch_ingest_dense_flags(k, n, flag, mlen, c->cus, grid, c->st));
+    HIPCHK(c, scan_inclusive_u32(c->scratch, flag, flag_incl, n, c->st));
+    HIPCHK(c, scan_inclusive_u32(c->scratch, mlen, len_incl, n, c->st));
+    uint32_t tot[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(&tot[0], flag_incl + (n - 1), 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(&tot[1], len_incl + (n - 1), 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    *ndense = tot[0];
+    *nbytes = tot[1];
+    if (tot[1] > cap_bytes) return SKE_EINVAL;  // nothing written; *nbytes is the need
+    const IngestDense D{out->ids, out->offs, out->epoch, out->valid, out->at};
+    HIPCHK(c, launch_ingest_dense(msgs, k, flag_incl, len_incl, valid_dev, epoch_dev, n, D, c->cus, grid, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SKE_OK;
+}
+
 int ske_gen_id_width(const ske_gen_params_t *p) {
     if (!p || p->id_hi <= p->id_lo) return SKE_EINVAL;
     uint64_t x = p->id_hi - 1;

@@ -415,4 +415,28 @@ SKE_HD TpTime tp_time(int64_t epoch) {
 }
 SKE_HD uint32_t tp_bin(const TpTime &t) { return t.dow * 24u + t.hour; }
 
+// ---------------------------------------------------------------------------
+// ISO-8601 timestamps of the ingest fast path (sketch_ingest.hip): the fields
+// of an accepted "YYYY-MM-DD[?HH:MM:SS[.fff[fff]][+HH:MM|-HH:MM]]" as seconds
+// since 1970-01-01T00:00:00 UTC -- analysis.epoch_seconds(datetime.
+// fromisoformat(text)): a naive timestamp is UTC as written, an offset is
+// subtracted, a date-only form is midnight (hh = mm = ss = 0), the fraction is
+// dropped (it is non-negative, so that is the floor, also before 1970).
+// ---------------------------------------------------------------------------
+// days since 1970-01-01 of a proleptic Gregorian date (H. Hinnant's days_from_civil)
+SKE_HD int32_t days_from_civil(int32_t y, uint32_t m, uint32_t d) {
+    y -= m <= 2;
+    const int32_t era = (y >= 0 ? y : y - 399) / 400;
+    const uint32_t yoe = uint32_t(y - era * 400);
+    const uint32_t doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + d - 1;
+    const uint32_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
+    return era * 146097 + int32_t(doe) - 719468;
+}
+// off_sign: +1 / -1 for a "+HH:MM" / "-HH:MM" offset of oh hours om minutes, 0 for none
+SKE_HD int64_t iso_epoch(uint32_t y, uint32_t mo, uint32_t d, uint32_t hh, uint32_t mi, uint32_t ss,
+                         int32_t off_sign, uint32_t oh, uint32_t om) {
+    const int64_t local = int64_t(days_from_civil(int32_t(y), mo, d)) * 86400 + int32_t(hh * 3600 + mi * 60 + ss);
+    return local - int64_t(off_sign) * int32_t(oh * 3600 + om * 60);
+}
+
 }  // namespace ske

@@ -106,6 +106,9 @@ struct ske_ctx {
     // lane); for small-shape tests and A/B timing, neither changes a result
     int tp_grid = 0;
     int tp_form = 0;
+    // workgroups of ske_ingest_times / ske_ingest_dense (SKE_INGEST_GRID, read by
+    // ske_open; 0: the ingest kernels' launch shape); for small-shape tests, changes no result
+    int ingest_grid = 0;
     uint8_t *regs = nullptr;  // nslots * 16384
     uint32_t nslots = 0;
     double *tau = nullptr, *sig = nullptr;  // device estimator tables (lazy)

@@ -22,6 +22,11 @@
 // span, the UTC day (README key form) and a 128-bit key hash; a device
 // open-addressing table maps key hashes to HLL slots (the host inserts keys
 // the first time it sees them).
+//
+// Behind the decode, for the per-student and per-day counters (DESIGN.md
+// section 12): k_ingest_times turns the accepted timestamp spans into epoch
+// seconds, k_ingest_dense compacts the decoded messages -- id bytes, epoch,
+// BF.EXISTS byte, message index -- into one packed batch.
 #include "sketch_common.h"
 #include "sketch_internal.h"
 
@@ -51,16 +56,6 @@ struct Reader {
 
 __device__ __forceinline__ bool is_ws(uint32_t c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; }
 __device__ __forceinline__ bool is_digit(uint32_t c) { return c - '0' < 10u; }
-
-// days since 1970-01-01 of a proleptic Gregorian date (H. Hinnant's days_from_civil)
-__device__ __forceinline__ int32_t days_from_civil(int32_t y, uint32_t m, uint32_t d) {
-    y -= m <= 2;
-    const int32_t era = (y >= 0 ? y : y - 399) / 400;
-    const uint32_t yoe = uint32_t(y - era * 400);
-    const uint32_t doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + d - 1;
-    const uint32_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
-    return era * 146097 + int32_t(doe) - 719468;
-}
 
 __device__ __forceinline__ bool leap(int32_t y) { return (y % 4 == 0 && y % 100 != 0) || y % 400 == 0; }
 
@@ -330,10 +325,136 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+namespace {
+
+// two decimal digits at bytes o, o + 1 of v
+__device__ __forceinline__ uint32_t dig2(uint64_t v, uint32_t o) {
+    return (uint32_t(v >> (8 * o)) & 0xffu) * 10 + (uint32_t(v >> (8 * o + 8)) & 0xffu) - 11u * '0';
+}
+
+}  // namespace
+
+// The epoch of every decoded message's timestamp span (0 for the others).
+// k_ingest_parse accepted the span, so its length names its form -- 10 date
+// only, 19 / 23 / 26 the time without and with a 3 or 6 digit fraction, 25 /
+// 29 / 32 the same followed by an offset -- and the fields are read by
+// position.  The span is at most 32 bytes: up to five aligned words, only
+// those that hold a byte of it, shifted into v[k] = span bytes 8k .. 8k + 7.
+__global__ void __launch_bounds__(256)
+    k_ingest_times(const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ status,
+                   const uint32_t *__restrict__ ts_start, const uint32_t *__restrict__ ts_len, uint64_t n,
+                   int64_t *__restrict__ epoch) {
+    const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+    for (uint64_t m = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; m < n; m += stride) {
+        int64_t ep = 0;
+        if (status[m] == 0) {
+            const uint32_t s = ts_start[m], len = ts_len[m], e = s + len;
+            const uint32_t a = s & ~7u, sh = (s & 7) * 8;
+            const uint64_t *wp = reinterpret_cast<const uint64_t *>(msgs + a);
+            uint64_t w[5], v[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 5; k++) w[k] = a + 8 * k < e ? wp[k] : 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) v[k] = sh ? (w[k] >> sh) | (w[k + 1] << (64 - sh)) : w[k];
+            const uint32_t y = dig2(v[0], 0) * 100 + dig2(v[0], 2), mo = dig2(v[0], 5), d = dig2(v[1], 0);
+            uint32_t hh = 0, mi = 0, ss = 0, oh = 0, om = 0;
+            int32_t sign = 0;
+            if (len > 10) {
+                hh = dig2(v[1], 3);
+                mi = dig2(v[1], 6);
+                ss = dig2(v[2], 1);
+            }
+            if (len == 25 || len == 29 || len == 32) {  // the last six bytes: +HH:MM / -HH:MM
+                const uint64_t t = len == 25 ? (v[2] >> 24) | (v[3] << 40)
+                                             : (len == 29 ? (v[2] >> 56) | (v[3] << 8) : v[3] >> 16);
+                sign = (uint32_t(t) & 0xffu) == '-' ? -1 : 1;
+                oh = dig2(t, 1);
+                om = dig2(t, 4);
+            }
+            ep = iso_epoch(y, mo, d, hh, mi, ss, sign, oh, om);
+        }
+        epoch[m] = ep;
+    }
+}
+
+// what the dense batch scans: the decoded flag and the decoded messages' id lengths
+__global__ void __launch_bounds__(256)
+    k_ingest_dense_flags(const uint8_t *__restrict__ status, const uint32_t *__restrict__ id_len, uint64_t n,
+                         uint32_t *__restrict__ flag, uint32_t *__restrict__ mlen) {
+    const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+    for (uint64_t m = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; m < n; m += stride) {
+        const uint32_t take = status[m] == 0;
+        flag[m] = take;
+        mlen[m] = take ? id_len[m] : 0;
+    }
+}
+
+// Every decoded message, in message order, as one packed batch: entry r (the
+// exclusive scan of the flags) gets the id bytes at offs[r] (the exclusive scan
+// of the lengths), the epoch, the BF.EXISTS byte and the message index.  An id
+// is read as aligned words (load_le: only words that hold a byte of it, so
+// never past the buffer's last 8-byte boundary) -- one or two loads for the
+// ids of the configs where k_ingest_pack's byte loop makes one per byte -- and
+// written byte by byte: neighbouring entries share the words of the output.
+__global__ void __launch_bounds__(256)
+    k_ingest_dense(const uint8_t *__restrict__ msgs, const uint8_t *__restrict__ status,
+                   const uint32_t *__restrict__ id_start, const uint32_t *__restrict__ id_len,
+                   const uint32_t *__restrict__ flag_incl, const uint32_t *__restrict__ len_incl,
+                   const uint8_t *__restrict__ valid, const int64_t *__restrict__ epoch, uint64_t n,
+                   IngestDense out) {
+    const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+    for (uint64_t m = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; m < n; m += stride) {
+        const uint32_t take = status[m] == 0;
+        const uint32_t len = take ? id_len[m] : 0;
+        const uint32_t r = flag_incl[m] - take, pos = len_incl[m] - len;
+        if (take) {
+            const uint8_t *src = msgs + id_start[m];
+            uint8_t *dst = out.ids + pos;
+            for (uint32_t j = 0; j < len; j += 8) {
+                const uint32_t nb = len - j < 8 ? len - j : 8;
+                const uint64_t w = load_le(src + j, nb);
+                for (uint32_t b = 0; b < nb; b++) dst[j + b] = uint8_t(w >> (8 * b));
+            }
+            out.offs[r] = pos;
+            out.epoch[r] = epoch ? epoch[m] : 0;
+            out.valid[r] = valid ? valid[m] : 0;
+            out.at[r] = uint32_t(m);
+        }
+        if (m == n - 1) out.offs[flag_incl[m]] = len_incl[m];
+    }
+}
+
 static inline unsigned grid_for(uint64_t n, unsigned block, unsigned cap) {
     uint64_t g = (n + block - 1) / block;
     if (g < 1) g = 1;
     return unsigned(g < cap ? g : cap);
+}
+
+// the two kernels above and the flags take `grid` workgroups when it is not 0
+// (SKE_INGEST_GRID: a small batch then walks the stride loop)
+hipError_t launch_ingest_times(const uint8_t *msgs, const IngestCols &c, uint64_t n, int64_t *epoch, int cus,
+                               unsigned grid, hipStream_t st) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_ingest_times, dim3(grid ? grid : grid_for(n, 256, cus * 16)), dim3(256), 0, st, msgs,
+                       c.status, c.ts_start, c.ts_len, n, epoch);
+    return hipGetLastError();
+}
+
+hipError_t launch_ingest_dense_flags(const IngestCols &c, uint64_t n, uint32_t *flag, uint32_t *mlen, int cus,
+                                     unsigned grid, hipStream_t st) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_ingest_dense_flags, dim3(grid ? grid : grid_for(n, 256, cus * 16)), dim3(256), 0, st,
+                       c.status, c.id_len, n, flag, mlen);
+    return hipGetLastError();
+}
+
+hipError_t launch_ingest_dense(const uint8_t *msgs, const IngestCols &c, const uint32_t *flag_incl,
+                               const uint32_t *len_incl, const uint8_t *valid, const int64_t *epoch, uint64_t n,
+                               const IngestDense &out, int cus, unsigned grid, hipStream_t st) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_ingest_dense, dim3(grid ? grid : grid_for(n, 256, cus * 16)), dim3(256), 0, st, msgs,
+                       c.status, c.id_start, c.id_len, flag_incl, len_incl, valid, epoch, n, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_ingest_parse(const uint8_t *msgs, const uint32_t *moffs, uint64_t n, int day_form,

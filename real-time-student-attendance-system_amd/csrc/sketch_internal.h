@@ -125,6 +125,22 @@ hipError_t launch_ingest_pack(const uint8_t *msgs, const IngestCols &c, const ui
 hipError_t launch_ingest_unpack(const IngestCols &c, const uint32_t *slot, const uint32_t *flag_incl,
                                 const uint8_t *kvalid, uint64_t n, uint8_t *valid, int cus,
                                 hipStream_t st);
+// the decoded messages as one packed batch (ske_ingest_dense_t)
+struct IngestDense {
+    uint8_t *ids;
+    uint32_t *offs;
+    int64_t *epoch;
+    uint8_t *valid;
+    uint32_t *at;
+};
+// grid: workgroups (0: the launch shape of the kernels above)
+hipError_t launch_ingest_times(const uint8_t *msgs, const IngestCols &c, uint64_t n, int64_t *epoch, int cus,
+                               unsigned grid, hipStream_t st);
+hipError_t launch_ingest_dense_flags(const IngestCols &c, uint64_t n, uint32_t *flag, uint32_t *mlen, int cus,
+                                     unsigned grid, hipStream_t st);
+hipError_t launch_ingest_dense(const uint8_t *msgs, const IngestCols &c, const uint32_t *flag_incl,
+                               const uint32_t *len_incl, const uint8_t *valid, const int64_t *epoch, uint64_t n,
+                               const IngestDense &out, int cus, unsigned grid, hipStream_t st);
 
 // sketch_xr.hip -- XCD-partitioned K1 for chains larger than the LDS image
 bool xr_supported(const ChainDev &ch);
@@ -286,7 +302,7 @@ enum ScratchSlot : int {
     kScrSortTmp,       //   rocprim radix sort temporary,
     kScrScanKeyTmp,    //   rocprim scan-by-key temporary
     kScrScanTmp,       // scan_inclusive_u32's rocprim temporary: ske_bf_madd, ske_keytab_lookup,
-                       // ske_ingest_swipes (synchronous calls, never at once)
+                       // ske_ingest_swipes, ske_ingest_dense (synchronous calls, never at once)
     kScrBfHa,          // ske_bf_madd: item hashes a,
     kScrBfHb,          //   hashes b,
     kScrBfState,       //   candidate state,
@@ -295,11 +311,11 @@ enum ScratchSlot : int {
     kScrBfPos,         //   their prefix count
     kScrMergePartial,  // ske_hll_pfmerge over > 256 sources: partial maxima
     kScrKtFlag,        // key table lookup (ske_keytab_lookup, ske_ingest_swipes): found flags,
-    kScrKtLen,         //   id lengths of found keys
+    kScrKtLen,         //   id lengths of found keys | ske_ingest_dense: decoded flags, their id lengths
     kScrKtIncl,        // ske_keytab_lookup: prefix count of the flags
     kScrInSlot,        // ske_ingest_swipes: slot per message,
     kScrInFlagIncl,    //   prefix count of the flags,
-    kScrInLenIncl,     //   prefix sum of the id lengths,
+    kScrInLenIncl,     //   prefix sum of the id lengths (both also ske_ingest_dense's),
     kScrInIds,         //   packed ids,
     kScrInOffs,        //   their offsets,
     kScrInKslot,       //   their slots,

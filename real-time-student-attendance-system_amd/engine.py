@@ -13,7 +13,7 @@ import gc
 
 import numpy as np
 
-from ._lib import CmsInfo, Context, GenParams, HhInfo, SKE_HH_ID_BYTES, SKE_MEM_DEVICE, SKE_TP_BINS
+from ._lib import CmsInfo, Context, GenParams, HhInfo, IngestDense, SKE_HH_ID_BYTES, SKE_MEM_DEVICE, SKE_TP_BINS
 from . import synthetic
 
 PASS_KINDS = 9  # SKE_PASS_KINDS (include/sketch.h)
@@ -315,15 +315,17 @@ class SketchEngine:
         items whose mask byte equals ``want`` -- K1's answers read in place.
         A fixed-width batch is only enqueued (ske_cms_add_fixed_async, after
         swipes_fixed_async on the same stream, capturable; ``sync()`` waits);
-        a batch of bytes + offsets goes through ske_cms_incrby, which takes
-        no mask and returns when done."""
+        so is a masked batch of bytes + offsets (ske_cms_add_packed_async);
+        an unmasked one goes through ske_cms_incrby, which returns when done."""
         if b.width > 0:
             self.ctx.call("ske_cms_add_fixed_async", int(cid), C.c_void_p(b.bytes.ptr), b.width, b.n,
                           C.c_void_p(incr.ptr) if incr else None, C.c_void_p(mask.ptr) if mask else None,
                           int(want))
             return
         if mask is not None:
-            raise ValueError("a masked add needs a fixed-width batch")
+            self.ctx.call("ske_cms_add_packed_async", int(cid), C.c_void_p(b.bytes.ptr), C.c_void_p(b.offs.ptr),
+                          b.n, C.c_void_p(incr.ptr) if incr else None, C.c_void_p(mask.ptr), int(want))
+            return
         self.ctx.call("ske_cms_incrby", int(cid), C.c_void_p(b.bytes.ptr), C.c_void_p(b.offs.ptr), b.n,
                       C.c_void_p(incr.ptr) if incr else None, None, SKE_MEM_DEVICE)
 
@@ -364,14 +366,18 @@ class SketchEngine:
         byte equals ``want``) whose estimate in table ``cid`` is at least
         ``threshold`` joins set ``hid``.  A fixed-width batch is only enqueued
         (ske_hh_track_fixed_async, behind the batch's cms_add on the same
-        stream, capturable; ``sync()`` waits); a batch of bytes + offsets goes
-        through ske_hh_track, which takes no mask and returns when done."""
+        stream, capturable; ``sync()`` waits); so is a masked batch of bytes +
+        offsets (ske_hh_track_packed_async: an id over 16 bytes is skipped and
+        turns ``complete`` false); an unmasked one goes through ske_hh_track,
+        which returns when done."""
         if b.width > 0:
             self.ctx.call("ske_hh_track_fixed_async", int(hid), int(cid), C.c_void_p(b.bytes.ptr), b.width, b.n,
                           C.c_void_p(mask.ptr) if mask else None, int(want), int(threshold))
             return
         if mask is not None:
-            raise ValueError("a masked track needs a fixed-width batch")
+            self.ctx.call("ske_hh_track_packed_async", int(hid), int(cid), C.c_void_p(b.bytes.ptr),
+                          C.c_void_p(b.offs.ptr), b.n, C.c_void_p(mask.ptr), int(want), int(threshold))
+            return
         self.ctx.call("ske_hh_track", int(hid), int(cid), C.c_void_p(b.bytes.ptr), C.c_void_p(b.offs.ptr), b.n,
                       int(threshold), SKE_MEM_DEVICE)
 
@@ -405,6 +411,23 @@ class SketchEngine:
         self.ctx.call("ske_tp_add_async", int(tid), C.c_void_p(epoch.ptr), int(n),
                       C.c_void_p(mask.ptr) if mask else None, int(want), int(late_from),
                       C.c_void_p(late.ptr) if late else None)
+
+    # ---- ingest: the decoded messages' times, and the decoded messages as one packed batch
+    def ingest_times(self, msgs: DeviceBuffer, cols, n: int, epoch: DeviceBuffer):
+        """ske_ingest_times: ``epoch[i]`` = message i's timestamp as seconds
+        since 1970-01-01 UTC where ``ske_ingest_parse`` (``cols``, an
+        ``IngestCols``) decoded it, else 0.  Only enqueued."""
+        self.ctx.call("ske_ingest_times", C.c_void_p(msgs.ptr), C.byref(cols), int(n), C.c_void_p(epoch.ptr))
+
+    def ingest_dense(self, msgs: DeviceBuffer, cols, n: int, out: IngestDense, cap_bytes: int,
+                     valid: DeviceBuffer | None = None, epoch: DeviceBuffer | None = None) -> tuple[int, int]:
+        """ske_ingest_dense: the decoded messages, in order, packed into
+        ``out``'s device arrays; returns ``(ndense, nbytes)``."""
+        nd, nb = C.c_uint64(), C.c_uint64()
+        self.ctx.call("ske_ingest_dense", C.c_void_p(msgs.ptr), C.byref(cols), int(n),
+                      C.c_void_p(valid.ptr) if valid else None, C.c_void_p(epoch.ptr) if epoch else None,
+                      C.byref(out), int(cap_bytes), C.byref(nd), C.byref(nb))
+        return int(nd.value), int(nb.value)
 
     # ---- HIP graphs: record enqueue-only calls once, replay many times
     def capture(self, fn) -> "Graph":

@@ -21,7 +21,7 @@ import numpy as np
 
 from .client import SketchClient
 from .config import AttendanceConfig
-from .encoding import encode
+from .encoding import encode, pack
 from .exceptions import ResponseError
 from .keyspace import day_key
 
@@ -29,8 +29,13 @@ logger = logging.getLogger(__name__)
 
 
 class AttendanceProcessor:
-    def __init__(self, client: SketchClient | None = None, config: AttendanceConfig | None = None):
+    def __init__(self, client: SketchClient | None = None, config: AttendanceConfig | None = None,
+                 counts=None):
+        """``counts``: a ``StudentCounts`` of the same client (default None:
+        nothing is counted); every acknowledged row's swipe then counts in it
+        (``count_packed``), which is what ``insights`` reads."""
         self.config = config or AttendanceConfig()
+        self.counts = counts
         # attendance_processor.py:37-41
         self.redis_client = client or SketchClient(decode_responses=True, device=self.config.device)
         self.acked = 0
@@ -108,7 +113,27 @@ class AttendanceProcessor:
             for r, v in zip(rows, valid):
                 r["is_valid"] = bool(v)
             self.acked += len(rows)
+            if self.counts is not None:  # the rows the reference inserts, invalid ones included
+                buf, offs = pack(ids)
+                self.counts.count_packed(buf, offs, valid,
+                                         [r["timestamp"] for r in rows] if self.counts.timed else None)
         return rows
+
+    def insights(self, keys: Sequence[str] | None = None, k: int = 3, **thresholds) -> list:
+        """attendance_analysis.py:65-118 in its order: ``counts.insights(
+        **thresholds)`` and, when ``keys`` (lecture-day HLL keys) are given,
+        "Lecture Attendance Rankings" (``lecture_rankings(keys, k)``, :87-97)
+        at its place, after the per-day entries and before the per-student
+        lists of :99-118."""
+        if self.counts is None:
+            raise ValueError("insights need a StudentCounts (counts=)")
+        out = self.counts.insights(**thresholds)
+        if keys is not None:
+            at = sum(1 for i in out if i["title"] in ("Habitual Latecomers", "Attendance by Day"))
+            out.insert(at, {"title": "Lecture Attendance Rankings",
+                            "description": "Most and least attended lectures",
+                            "data": lecture_rankings(self.redis_client, keys, k)})
+        return out
 
     def process_attendance(self, source: Iterable, batch_size: int | None = None):
         """attendance_processor.py:94-141 over an in-memory message source;

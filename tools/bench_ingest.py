@@ -9,9 +9,19 @@ Messages follow the reference generator's schema (data_generator.py:112-118):
 "LECTURE_<YYYYMMDD>", "is_valid": ..., "event_type": ...}, C2-sized: 100k
 students (10 % invalid swipes), 50 lecture days.  The timed region includes
 the host-side packing and the H2D copy of the payloads (PCIe), so the rate is
-end to end.  usage: python tools/bench_ingest.py [--messages N] [--reps R]
+end to end.
+
+"insight_stages" times what ``StudentCounts.update_messages`` adds behind the
+ingest, over the same batch in one session: the device stages one by one
+(host clock around calls that end in a stream synchronise, ``--inner`` calls
+per timing, best and median of ``--reps``) beside the two ingest kernels
+they follow, ske_ingest_parse and ske_ingest_swipes; the whole
+``update_messages_packed`` call; and the host alternative, ``count_packed``
+fed by per-message json.loads + fromisoformat, on the CPU sample.
+usage: python tools/bench_ingest.py [--messages N] [--reps R]
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -40,11 +50,82 @@ def make_messages(rng, n, members, invalid):
     return out
 
 
+def timed(fn, sync, reps, inner):
+    """best and median seconds of one fn() call followed through to the device's end"""
+    fn()
+    sync()
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        for _ in range(inner):
+            fn()
+        sync()
+        out.append((time.perf_counter() - t0) / inner)
+    return {"best_s": min(out), "median_s": float(np.median(out))}
+
+
+def insight_stages(pkg, client, msgs, blob, moffs, reps, inner, cpu_messages):
+    """The stages behind the ingest that turn the decoded messages into the
+    counters of ``StudentCounts`` (every option on), each over the whole batch."""
+    from datetime import datetime
+    from rtsas_amd._lib import IngestDense
+    n = len(msgs)
+    sc = pkg.StudentCounts(client, track_attended=40, track_invalid=5, late_key="cms:late", track_late=20,
+                           day_profile="week")
+    valid, status = sc.update_messages_packed("bf:students", blob, moffs)  # warm: buffers, keys
+    ctx, fid = client.ctx, client.keys.fid[b"bf:students"]
+    run = client._ingest_batch("bf:students", blob, moffs, "hll:unique:", "readme")[2]
+    B, cols = run.B, run.cols
+    d = sc._packed_buffers("dense", n, B["msgs"].nbytes)
+    msgs_p, moffs_p = C.c_void_p(B["msgs"].ptr), C.c_void_p(B["moffs"].ptr)
+    out = IngestDense(*[C.c_void_p(d[k].ptr) for k in ("ids", "offs", "epoch", "valid", "at")])
+    nd, nb, taken = C.c_uint64(), C.c_uint64(), C.c_uint64()
+
+    def sync():
+        ctx.call("ske_sync")
+
+    def dense():
+        ctx.call("ske_ingest_dense", msgs_p, C.byref(cols), n, C.c_void_p(B["valid"].ptr),
+                 C.c_void_p(d["epoch_all"].ptr), C.byref(out), d["nbytes"], C.byref(nd), C.byref(nb))
+    stages = {
+        "ske_ingest_parse": lambda: ctx.call("ske_ingest_parse", msgs_p, moffs_p, n, 1, C.byref(cols)),
+        "ske_ingest_swipes": lambda: ctx.call("ske_ingest_swipes", fid, msgs_p, C.byref(cols), n,
+                                              C.c_void_p(B["valid"].ptr), C.byref(taken)),
+        "ske_ingest_times": lambda: ctx.call("ske_ingest_times", msgs_p, C.byref(cols), n,
+                                             C.c_void_p(d["epoch_all"].ptr)),
+        "ske_ingest_dense": dense,
+    }
+    res = {k: timed(f, sync, reps, inner) for k, f in stages.items()}
+    ndense = int(nd.value)
+    res["packed_adds_and_tracks"] = timed(
+        lambda: sc._enqueue_packed(d["ids"], d["offs"], ndense, d["valid"], d["epoch"], d["late"]), sync, reps, inner)
+    res["packed_adds_and_tracks"]["calls"] = "3 ske_cms_add_packed_async, ske_tp_add_async, 3 ske_hh_track_packed_async"
+    res["update_messages_packed"] = timed(lambda: sc.update_messages_packed("bf:students", blob, moffs),
+                                          sync, reps, 1)
+    res["ingest_packed"] = timed(lambda: client.ingest_packed("bf:students", blob, moffs), sync, reps, 1)
+    # the host alternative: every message decoded by Python, then count_packed
+    sample = msgs[:cpu_messages]
+    t0 = time.perf_counter()
+    ids, tss = [], []
+    for m in sample:
+        data = json.loads(m.decode())
+        ids.append(pkg.encode(data["student_id"]))
+        tss.append(datetime.fromisoformat(data["timestamp"]))
+    t_decode = time.perf_counter() - t0
+    buf, offs = pkg.pack(ids)
+    cp = timed(lambda: sc.count_packed(buf, offs, valid[:len(sample)], tss), sync, reps, 1)
+    res["host_alternative"] = {"sample": len(sample), "decode_s": t_decode, "count_packed": cp,
+                               "messages_per_s": len(sample) / (t_decode + cp["best_s"])}
+    return {"messages": n, "dense": ndense, "dense_id_bytes": int(nb.value), "inner": inner, "stages": res,
+            "update_messages_per_s": n / res["update_messages_packed"]["best_s"]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--messages", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cpu-messages", type=int, default=50_000)
+    ap.add_argument("--inner", type=int, default=20, help="calls per timing of one device stage")
     args = ap.parse_args()
     pkg = ge.load_package()
     orc = ge.load_oracle()
@@ -88,6 +169,7 @@ def main():
             hlls.setdefault(f"hll:unique:{data['lecture_id']}:{ts.date().isoformat()}",
                             orc.HLL()).add(sid)
     cpu_s = time.perf_counter() - t0
+    stages = insight_stages(pkg, client, msgs, blob, moffs, args.reps, args.inner, args.cpu_messages)
     print(json.dumps({
         "metric": "ingested swipes/s (packed JSON payloads in host memory -> answers + PFADD), end to end",
         "messages": args.messages, "payload_bytes": int(sum(len(m) for m in msgs)),
@@ -98,6 +180,7 @@ def main():
         "cpu_reference_loop": {"value": len(sample) / cpu_s, "unit": "swipes/s", "cores": 1,
                                "sample": f"{len(sample)} messages, json.loads + fromisoformat + "
                                          "oracle BF.EXISTS / PFADD per event"},
+        "insight_stages": stages,
     }), flush=True)
 
 
