@@ -90,6 +90,7 @@ extern "C" {
 #define SKE_HH_ID_BYTES 16   /* the longest id a heavy-hitter set holds */
 #define SKE_HH_MAX_PROBES 128 /* slots one insert looks at before it gives up */
 #define SKE_HH_LOAD_DEN 2    /* new ids are refused once used >= capacity / SKE_HH_LOAD_DEN */
+#define SKE_HH_MAX_RANKS 16  /* ranks one ske_hh_select carries */
 #define SKE_MAX_TP 256
 #define SKE_TP_BINS 168      /* weekday * 24 + hour, Monday = 0 */
 #define SKE_HLL_REGISTERS 16384
@@ -366,6 +367,36 @@ int ske_hh_track(ske_ctx *ctx, uint32_t hid, uint32_t cid, const uint8_t *bytes,
  * (cap >= used always suffices).  *complete = 0 once an insert was refused. */
 int ske_hh_list(ske_ctx *ctx, uint32_t hid, uint32_t cid, uint32_t threshold, uint8_t *out_ids,
                 uint32_t *out_lens, uint32_t *out_est, uint64_t cap, uint64_t *n_out, int *complete);
+/* The statistics of a set's current estimates, computed on the device: over
+ * the members whose estimate in table cid is >= threshold (0 is legal: every
+ * member), their number, the exact sums of the estimates and of their squares,
+ * the extremes and the two middle order statistics (the median is their mean).
+ * A set tracked at threshold 1 holds every id that ever counted, so these are
+ * the population statistics of attendance_analysis.py:68-69 and :99-103.  All
+ * integer arithmetic: exact, and identical from run to run.  A square is
+ * split into its low and high 32 bits and the halves are summed apart; at the
+ * largest set (2^SKE_HH_MAX_LOG2 members) each sum stays below 2^56, so
+ * neither overflows nor carries into the other.  Nothing but this struct
+ * crosses to the host.  Neither call changes the set or the table; both
+ * return when done and, as ske_hh_reset, answer SKE_EBUSY while a capture is
+ * recording.  SKE_EHHNOSET / SKE_ECMSNOKEY as ske_hh_list. */
+typedef struct {
+    uint64_t n;              /* members whose current estimate is >= threshold */
+    uint64_t sum;            /* of those estimates */
+    uint64_t sq_lo, sq_hi;   /* sum of squares = sq_hi * 2^32 + sq_lo (each word below 2^56) */
+    uint32_t min, max;       /* 0, 0 when n == 0 */
+    uint32_t med_lo, med_hi; /* the (n-1)/2-th and n/2-th smallest (0-based); 0, 0 when n == 0 */
+    uint32_t complete;       /* 0 once an insert was refused, as ske_hh_list */
+    uint32_t reserved;       /* 0 */
+} ske_hh_stats_t;            /* 56 bytes */
+int ske_hh_stats(ske_ctx *ctx, uint32_t hid, uint32_t cid, uint32_t threshold, ske_hh_stats_t *out);
+/* out_est[j] = the ranks[j]-th smallest passing estimate (0-based; ranks in any
+ * order, repeats allowed; 1 <= nranks <= SKE_HH_MAX_RANKS, else SKE_EINVAL): a
+ * radix select on the device, 8 bits a round.  *n_out = how many pass; any
+ * ranks[j] >= *n_out: SKE_EINVAL, *n_out is still written and out_est is not
+ * touched. */
+int ske_hh_select(ske_ctx *ctx, uint32_t hid, uint32_t cid, uint32_t threshold, const uint64_t *ranks,
+                  uint32_t nranks, uint32_t *out_est, uint64_t *n_out);
 
 /* ---- time profile: weekday x hour counters of the swipes' times ----
  * SKE_TP_BINS u64 counters on the device, addressed by a caller-chosen tid <

@@ -56,6 +56,7 @@ SKE_HH_MAX_LOG2 = 24
 SKE_HH_ID_BYTES = 16
 SKE_HH_MAX_PROBES = 128
 SKE_HH_LOAD_DEN = 2
+SKE_HH_MAX_RANKS = 16
 SKE_MAX_TP = 256
 SKE_TP_BINS = 168
 HLL_REGISTERS = 16384
@@ -88,6 +89,13 @@ class CmsInfo(C.Structure):
 
 class HhInfo(C.Structure):
     _fields_ = [("capacity", C.c_uint64), ("used", C.c_uint64), ("overflow", C.c_uint64)]
+
+
+class HhStats(C.Structure):
+    """ske_hh_stats_t (include/sketch.h)."""
+    _fields_ = [("n", C.c_uint64), ("sum", C.c_uint64), ("sq_lo", C.c_uint64), ("sq_hi", C.c_uint64),
+                ("min", C.c_uint32), ("max", C.c_uint32), ("med_lo", C.c_uint32), ("med_hi", C.c_uint32),
+                ("complete", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class IngestCols(C.Structure):
@@ -178,6 +186,9 @@ SIGNATURES = {
     "ske_hh_track": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, _u8p, _u32p, C.c_uint64, C.c_uint32, C.c_int]),
     "ske_hh_list": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_uint32, _u8p, _u32p, _u32p, C.c_uint64,
                               C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "ske_hh_stats": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(HhStats)]),
+    "ske_hh_select": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, C.c_uint32, _u32p,
+                                C.POINTER(C.c_uint64)]),
     "ske_tp_init": (C.c_int, [_CTX, C.c_uint32]),
     "ske_tp_free": (C.c_int, [_CTX, C.c_uint32]),
     "ske_tp_reset": (C.c_int, [_CTX, C.c_uint32]),

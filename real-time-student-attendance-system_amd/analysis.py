@@ -32,6 +32,7 @@ counters in place (DESIGN.md "Insights from the message stream");
 from __future__ import annotations
 
 import ctypes as C
+import math
 from datetime import datetime, timedelta, timezone
 
 import numpy as np
@@ -39,7 +40,7 @@ import numpy as np
 from ._lib import IngestDense, SKE_MEM_DEVICE
 from .client_ingest import join_messages
 from .encoding import encode, pack
-from .engine import DeviceBuffer
+from .engine import DeviceBuffer, hh_list
 
 
 DAY_NAMES = ("Monday", "Tuesday", "Wednesday", "Thursday", "Friday", "Saturday", "Sunday")
@@ -72,6 +73,36 @@ def epoch_seconds(times) -> np.ndarray:
             raise TypeError("times are int64 seconds, datetime64 values or datetime objects")
         out[i] = (t - (_EPOCH if t.tzinfo is None else _EPOCH_UTC)) // _SECOND
     return out
+
+
+def reference_rule(stats: dict, rule: str):
+    """The smallest integer estimate that passes one of the reference's two
+    population rules, from ``hh_stats``' exact integers (``n``, ``sum``,
+    ``sumsq``, ``median``); None when nothing can pass.
+
+    ``"median"``: ``est > median`` (attendance_analysis.py:69).  Twice the
+    median is the integer M = med_lo + med_hi, so the rule is ``2 * est > M``.
+
+    ``"median+std"``: ``est > median + std`` (:101-103), std the sample
+    standard deviation sqrt(V / k) with V = n * sumsq - sum * sum and
+    k = n * (n - 1).  With x = 2 * est - M the rule reads x > 2 * sqrt(V / k):
+    x is positive and x * x * k > 4 * V.  x * x is an integer, so that is
+    x * x > floor(4 * V / k), i.e. x >= isqrt(floor(4 * V / k)) + 1 -- Python
+    ints throughout, no float is compared.  ``n == 1``: pandas' std is NaN and
+    nothing compares greater."""
+    n = int(stats["n"])
+    if rule not in ("median", "median+std"):
+        raise ValueError('rule is "median" or "median+std"')
+    if n == 0:
+        return None
+    twice_median = int(round(2 * stats["median"]))  # med_lo + med_hi: exact, both below 2^32
+    if rule == "median":
+        return twice_median // 2 + 1
+    if n == 1:
+        return None
+    s = int(stats["sum"])
+    x = math.isqrt(4 * (n * int(stats["sumsq"]) - s * s) // (n * (n - 1))) + 1
+    return (x + twice_median + 1) // 2
 
 
 class StudentCounts:
@@ -363,13 +394,54 @@ class StudentCounts:
         """Estimated invalid attempts of each id."""
         return self._query(self.invalid_key, ids)
 
-    def _top(self, key, k, threshold):
+    def _track_of(self, key):
+        """(set name, track threshold) of a tracked key."""
         name = b"hh:" + encode(key)
         track = [t for t in self._tracks + [self._late_track] if t is not None and t[0] == name]
         if not track:
             raise ValueError(f"{key} is not tracked (track_attended / track_invalid / track_late)")
-        thr = track[0][1] if threshold is None else int(threshold)
-        if thr < track[0][1]:
+        return name, track[0][1]
+
+    def _which_key(self, which: str):
+        keys = {"attended": self.attended_key, "invalid": self.invalid_key, "late": self.late_key}
+        if which not in keys:
+            raise ValueError('which is "attended", "invalid" or "late"')
+        if keys[which] is None:
+            raise ValueError("no late_key is tracked (track_late)")
+        return keys[which]
+
+    def population(self, which: str) -> dict:
+        """``client.hh_stats`` of the key's set at its track threshold: the
+        statistics of every tracked student's estimate -- with a track
+        threshold of 1 the reference's whole population -- computed on the
+        device.  ``which``: "attended", "invalid" or "late"."""
+        name, thr = self._track_of(self._which_key(which))
+        return self.client.hh_stats(name, thr)
+
+    def reference_threshold(self, which: str, rule: str):
+        """The smallest integer estimate that passes the reference's rule over
+        ``population(which)``: ``rule="median+std"`` is ``est > median + std``
+        (attendance_analysis.py:101-103), ``"median"`` is ``est > median``
+        (:69); decided in integers (``reference_rule``).  None when nothing can
+        pass: no student, or one student under ``"median+std"``."""
+        return reference_rule(self.population(which), rule)
+
+    def _top_reference(self, key, rule: str):
+        """``_top`` at the threshold the reference's rule derives on the
+        device: ske_hh_stats, then ske_hh_list at that threshold, so only the
+        passing students cross to the host."""
+        name, thr = self._track_of(key)
+        stats = self.client.hh_stats(name, thr)
+        derived = reference_rule(stats, rule)
+        if derived is None or derived > 0xFFFFFFFF:  # nobody can pass
+            return [], np.zeros(0, np.uint32), stats["complete"]
+        hid, cid = self.client._hh_entry(name)
+        return hh_list(self.client.ctx, hid, cid, derived, room=stats["n"])
+
+    def _top(self, key, k, threshold):
+        name, track_thr = self._track_of(key)
+        thr = track_thr if threshold is None else int(threshold)
+        if thr < track_thr:
             raise ValueError("a list threshold below the track threshold promises nothing")
         ids, est, complete = self.client.hh_list(name, thr)
         if k is not None:
@@ -414,26 +486,40 @@ class StudentCounts:
         per_day = self.by_hour_of_week().sum(axis=1)
         return {d: int(per_day[i]) for d, i in sorted((d, i) for i, d in enumerate(DAY_NAMES)) if per_day[i]}
 
-    def insights(self, attended_threshold: int | None = None, invalid_threshold: int | None = None,
-                 late_threshold: int | None = None) -> list:
+    def insights(self, attended_threshold: int | str | None = None, invalid_threshold: int | str | None = None,
+                 late_threshold: int | str | None = None) -> list:
         """The reference's per-student and per-day insights (attendance_
         analysis.py:65-85, :99-118) in its order, each only when its option is
         on: "Habitual Latecomers" (``track_late``), "Attendance by Day"
         (``day_profile``), then the two below.  ``data`` is ``{student_id:
         estimate}`` of the tracked keys, ``{day name: swipes}`` by day.
         The reference picks its consistent attendees by the median plus the
-        standard deviation of every student's count; a sketch holds no such
-        population, so the caller passes the thresholds (default: the track
-        thresholds).  ``complete`` is added to each per-student entry.
+        standard deviation of every student's count, its latecomers by the
+        median.  A set tracked at threshold 1 is that population -- every id
+        that ever counted, each with its current estimate -- so the string
+        ``"reference"`` as a threshold applies the reference's own rule:
+        ``attended_threshold="reference"`` lists ``est > median + std``,
+        ``late_threshold="reference"`` lists ``est > median``, both over the
+        key's set at its track threshold; the statistics are computed on the
+        device and the rule is decided in integers (``reference_threshold``),
+        then only the passing students are listed.  The reference lists every
+        invalid attempt, so ``invalid_threshold="reference"`` is the track
+        threshold.  An integer is a threshold of the caller's; the default is
+        the track threshold.  ``complete`` is added to each per-student entry.
 
-        Latecomers with ``late_threshold=None`` follow the reference's rule
-        over what the set holds: listed at the track threshold, a student
-        stays whose estimate is above the median of the listed estimates --
-        the reference's result when ``track_late`` is 1, the list is complete
-        and the estimates are exact.  An integer works as the other two."""
+        Latecomers with ``late_threshold=None`` follow the reference's rule on
+        the host: listed at the track threshold, a student stays whose
+        estimate is above the median of the listed estimates -- the same
+        students as ``"reference"``, the reference's result when ``track_late``
+        is 1, the list is complete and the estimates are exact."""
         out = []
+        if invalid_threshold == "reference":
+            invalid_threshold = None
         if self._late_track is not None:
-            ids, est, complete = self._top(self.late_key, None, late_threshold)
+            if late_threshold == "reference":
+                ids, est, complete = self._top_reference(self.late_key, "median")
+            else:
+                ids, est, complete = self._top(self.late_key, None, late_threshold)
             if late_threshold is None and len(ids):
                 keep = est > np.median(est)
                 ids, est = [i for i, k in zip(ids, keep) if k], est[keep]
@@ -453,7 +539,10 @@ class StudentCounts:
                  self.invalid_key, invalid_threshold)):
             if not any(t[0] == b"hh:" + encode(key) for t in self._tracks):
                 continue
-            ids, est, complete = self._top(key, None, thr)
+            if thr == "reference":  # the attended key: the invalid one's was resolved above
+                ids, est, complete = self._top_reference(key, "median+std")
+            else:
+                ids, est, complete = self._top(key, None, thr)
             out.append({"title": title, "description": text,
                         "data": {i.decode("utf-8", "replace"): int(e) for i, e in zip(ids, est)},
                         "complete": complete})

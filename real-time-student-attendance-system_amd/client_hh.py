@@ -8,12 +8,14 @@ sets, by name.  ``DEL`` of the bound CMS key and ``FLUSHALL`` free them; while
 no set exists neither makes any further native call."""
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 from . import _lib
 from ._lib import SKE_MEM_HOST, ptr as _ptr
 from .encoding import encode
-from .engine import hh_info, hh_list
+from .engine import hh_info, hh_list, hh_select, hh_stats
 from .exceptions import ResponseError
 
 
@@ -79,3 +81,55 @@ class HhMixin:
         is at least ``threshold``, largest first (engine.hh_list)."""
         hid, cid = self._hh_entry(name)
         return hh_list(self.ctx, hid, cid, threshold)
+
+    def hh_stats(self, name, threshold: int = 0) -> dict:
+        """The statistics of the members whose current estimate is at least
+        ``threshold`` (0: every member), computed on the device
+        (``derive_stats`` of engine.hh_stats): ``n``, ``sum``, ``sumsq``,
+        ``min``, ``max``, ``median``, ``mean``, ``std``, ``complete``."""
+        hid, cid = self._hh_entry(name)
+        return derive_stats(hh_stats(self.ctx, hid, cid, threshold))
+
+    def hh_select(self, name, ranks, threshold: int = 0) -> np.ndarray:
+        """The ``ranks[j]``-th smallest of those estimates (0-based, any order,
+        repeats allowed) as uint32; more than SKE_HH_MAX_RANKS ranks go in
+        several calls."""
+        hid, cid = self._hh_entry(name)
+        r = np.ascontiguousarray(ranks, dtype=np.uint64).reshape(-1)
+        step = _lib.SKE_HH_MAX_RANKS
+        parts = [hh_select(self.ctx, hid, cid, threshold, r[i:i + step]) for i in range(0, r.size, step)]
+        return np.concatenate(parts) if parts else np.zeros(0, np.uint32)
+
+    def hh_quantile(self, name, q: float, threshold: int = 0) -> float:
+        """The ``q``-quantile of those estimates as ``np.quantile`` computes it
+        by default: linear interpolation at position ``q * (n - 1)`` between
+        the two order statistics around it; ``nan`` over no member."""
+        q = float(q)
+        if not 0.0 <= q <= 1.0:
+            raise ValueError("a quantile is between 0 and 1")
+        hid, cid = self._hh_entry(name)
+        n = hh_stats(self.ctx, hid, cid, threshold)["n"]
+        if n == 0:
+            return float("nan")
+        pos = q * (n - 1)
+        lo = min(int(math.floor(pos)), n - 1)
+        hi = min(lo + 1, n - 1)
+        a, b = (float(v) for v in hh_select(self.ctx, hid, cid, threshold, [lo, hi]))
+        return a + (b - a) * (pos - lo)
+
+
+def derive_stats(raw: dict) -> dict:
+    """engine.hh_stats' integers as the dict ``hh_stats`` returns.  ``sumsq``
+    is a Python int; ``median`` is the mean of the two middle order statistics
+    (exact in float64); ``std`` is the sample standard deviation (``ddof=1``, as
+    pandas; ``nan`` when ``n < 2``) from the exact integer variance numerator
+    ``n * sumsq - sum * sum``: one correctly rounded division and one square
+    root, no float sum."""
+    n, s = raw["n"], raw["sum"]
+    sumsq = raw["sq_hi"] * 2 ** 32 + raw["sq_lo"]
+    nan = float("nan")
+    return {"n": n, "sum": s, "sumsq": sumsq, "min": raw["min"], "max": raw["max"],
+            "median": (raw["med_lo"] + raw["med_hi"]) / 2 if n else nan,
+            "mean": s / n if n else nan,
+            "std": math.sqrt((n * sumsq - s * s) / (n * (n - 1))) if n >= 2 else nan,
+            "complete": bool(raw["complete"])}

@@ -1,7 +1,8 @@
 // sketch_api_hh.cpp -- libsketch C-ABI (include/sketch.h): heavy-hitter sets
-// beside a Count-Min Sketch table (init, reset, info, track, list), kernels in
-// sketch_hh.hip.  A set holds no pointer to a table: every track and list looks
-// the table up by cid, so a freed table is an error, never a stale pointer.
+// beside a Count-Min Sketch table (init, reset, info, track, list: kernels in
+// sketch_hh.hip; stats, select: sketch_hh_stats.hip).  A set holds no pointer to
+// a table: every track, list, stats and select looks the table up by cid, so a
+// freed table is an error, never a stale pointer.
 #include <string.h>
 
 #include <algorithm>
@@ -12,7 +13,8 @@
 using namespace ske;
 
 static_assert(kHhMaxProbes == SKE_HH_MAX_PROBES && kHhLoadDen == SKE_HH_LOAD_DEN, "sketch.h states the kernels' bounds");
-static_assert((1u << SKE_HH_MIN_LOG2) % 256 == 0, "k_hh_list covers the slots with whole blocks");
+static_assert((1u << SKE_HH_MIN_LOG2) % 256 == 0, "k_hh_list and k_hhs_est cover the slots with whole blocks");
+static_assert(kHhStatRanks == SKE_HH_MAX_RANKS && sizeof(ske_hh_stats_t) == 56, "sketch.h states the select's ranks");
 
 namespace ske {
 
@@ -249,6 +251,68 @@ int ske_hh_list(ske_ctx *c, uint32_t hid, uint32_t cid, uint32_t threshold, uint
         out_lens[i] = v[i].len;
         out_est[i] = v[i].est;
     }
+    return SKE_OK;
+}
+
+}  // extern "C"
+
+// ske_hh_stats and ske_hh_select: the record zeroed, the whole chain of
+// kernels, one copy of the record's head, one wait.  R.n == 0: the medians.
+static int hh_stats_run(ske_ctx *c, uint32_t hid, uint32_t cid, uint32_t threshold, const HhRanks &R,
+                        HhStatDev *reply) {
+    Hh *H = get_hh(c, hid);
+    if (!H) return SKE_EHHNOSET;
+    Cms *T = get_cms(c, cid);
+    if (!T) return SKE_ECMSNOKEY;
+    if (c->capturing) {
+        c->last_hip = "ske_hh_stats / ske_hh_select wait for the stream and cannot be recorded";
+        return SKE_EBUSY;
+    }
+    int rc = SKE_OK;
+    HhStatDev *D = (HhStatDev *)stage_buf(c, kStgHhStat, sizeof(HhStatDev), &rc);
+    if (rc) return rc;
+    uint32_t *est = (uint32_t *)stage_buf(c, kStgHhSelEst, (size_t(1) << H->log2) * 4 + 16, &rc);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(D, 0, sizeof(HhStatDev), c->st));
+    HIPCHK(c, launch_hh_stats(table_of(*T), set_of(*H), threshold, R, D, est, c->cus, c->st));
+    HIPCHK(c, hipMemcpyAsync(reply, D, kHhStatReplyBytes, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SKE_OK;
+}
+
+extern "C" {
+
+int ske_hh_stats(ske_ctx *c, uint32_t hid, uint32_t cid, uint32_t threshold, ske_hh_stats_t *out) {
+    if (!c || !out) return SKE_EINVAL;
+    HhRanks R{};
+    HhStatDev r{};
+    const int rc = hh_stats_run(c, hid, cid, threshold, R, &r);
+    if (rc) return rc;
+    out->n = r.n;
+    out->sum = r.sum;
+    out->sq_lo = r.sq_lo;
+    out->sq_hi = r.sq_hi;
+    out->min = r.min;
+    out->max = r.max;
+    out->med_lo = r.prefix[0];
+    out->med_hi = r.prefix[1];
+    out->complete = r.complete;
+    out->reserved = 0;
+    return SKE_OK;
+}
+
+int ske_hh_select(ske_ctx *c, uint32_t hid, uint32_t cid, uint32_t threshold, const uint64_t *ranks, uint32_t nranks,
+                  uint32_t *out_est, uint64_t *n_out) {
+    if (!c || !ranks || !out_est || !n_out || nranks == 0 || nranks > SKE_HH_MAX_RANKS) return SKE_EINVAL;
+    HhRanks R{};
+    R.n = nranks;
+    for (uint32_t j = 0; j < nranks; j++) R.r[j] = ranks[j];
+    HhStatDev r{};
+    const int rc = hh_stats_run(c, hid, cid, threshold, R, &r);
+    if (rc) return rc;
+    *n_out = r.n;
+    if (r.bad) return SKE_EINVAL;
+    for (uint32_t j = 0; j < nranks; j++) out_est[j] = r.prefix[j];
     return SKE_OK;
 }
 

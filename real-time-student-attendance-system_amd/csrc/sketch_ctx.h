@@ -9,7 +9,7 @@
 //   sketch_api_swipes.cpp  K1: variant choice, launch_k1, ske_swipes*, ske_route_*
 //   sketch_api_ingest.cpp  ingest, the key table, the generator
 //   sketch_api_cms.cpp     Count-Min Sketch tables: init, add, query, merge, export / import
-//   sketch_api_hh.cpp      heavy-hitter sets beside a table: init, track, list
+//   sketch_api_hh.cpp      heavy-hitter sets beside a table: init, track, list, stats, select
 //   sketch_api_tp.cpp      time profiles (weekday x hour counters): init, add, read / import
 // A helper used by one unit is static there; what crosses units is declared here.
 #pragma once

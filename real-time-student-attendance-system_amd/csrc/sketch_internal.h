@@ -1,5 +1,7 @@
 // sketch_internal.h -- launcher declarations shared by the libsketch TUs.
 #pragma once
+#include <cstddef>
+
 #include "sketch_common.h"
 
 namespace ske {
@@ -260,6 +262,38 @@ hipError_t launch_hh_track(const CmsTable &T, const CmsItems &I, const HhSet &S,
 hipError_t launch_hh_list(const CmsTable &T, const HhSet &S, uint32_t threshold, uint32_t cap, uint64_t *out_ids,
                           uint32_t *out_len, uint32_t *out_est, unsigned int *out_n, hipStream_t st);
 
+// sketch_hh_stats.hip -- moments and order statistics of a set's current
+// estimates, all in integers.  One device record per
+// call; the host reads its first kHhStatReplyBytes bytes once, at the end.
+constexpr uint32_t kHhStatRanks = 16;  // ranks one select carries (SKE_HH_MAX_RANKS)
+struct HhStatDev {
+    // the estimate pass: one add of each per workgroup that has a passing slot
+    unsigned long long sum;           // of the passing estimates
+    unsigned long long sq_lo, sq_hi;  // of the low / high 32 bits of their squares
+    unsigned int n;                   // how many pass = entries of the compacted array
+    unsigned int nmin;                // max of ~estimate (zeroed with the record); k_hhs_begin turns it into
+    unsigned int min, max;            //   min (0 when n == 0)
+    unsigned int complete;            // the set's overflow word was 0 (k_hhs_begin)
+    unsigned int bad;                 // a requested rank was >= n: nothing is selected
+    unsigned int prefix[kHhStatRanks];  // per rank: the digits fixed so far; after the last round the value
+    // -- up to here the host's copy (kHhStatReplyBytes)
+    unsigned int nr;                         // ranks being selected (0: none)
+    unsigned int lead[kHhStatRanks];         // the first rank with the same prefix: it owns the histogram
+    unsigned long long rank[kHhStatRanks];   // the rank left among the values that match the prefix
+    unsigned int hist[kHhStatRanks * 256];   // per leading rank: the round's digit counts
+};
+constexpr size_t kHhStatReplyBytes = offsetof(HhStatDev, nr);
+struct HhRanks {
+    unsigned long long r[kHhStatRanks];
+    uint32_t n;  // 0: the two median ranks, (n - 1) / 2 and n / 2, derived on the device
+};
+// The whole chain on st, no host round trip: the estimate pass over S's slots
+// (passing estimates compacted into est, 4 bytes per slot at most, order
+// undefined), the ranks, then the select's rounds.  *D must be zeroed by the
+// caller (stream order).
+hipError_t launch_hh_stats(const CmsTable &T, const HhSet &S, uint32_t threshold, const HhRanks &R, HhStatDev *D,
+                           uint32_t *est, int cus, hipStream_t st);
+
 // sketch_tp.hip -- time profile: weekday x hour counters of a batch's swipe
 // times, and the per-swipe "late" byte
 struct TpArgs {
@@ -363,6 +397,8 @@ enum StageSlot : int {
     kStgHhIds,     // ske_hh_list: the entries' id words,
     kStgHhLen,     //   lengths,
     kStgHhEst,     //   estimates
+    kStgHhStat,    // ske_hh_stats / ske_hh_select: the accumulators, the rank state and the histograms (HhStatDev),
+    kStgHhSelEst,  //   the passing estimates, compacted (4 bytes per slot of the set)
     kStageSlotCount
 };
 

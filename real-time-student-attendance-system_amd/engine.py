@@ -13,7 +13,8 @@ import gc
 
 import numpy as np
 
-from ._lib import CmsInfo, Context, GenParams, HhInfo, IngestDense, SKE_HH_ID_BYTES, SKE_MEM_DEVICE, SKE_TP_BINS
+from ._lib import (CmsInfo, Context, GenParams, HhInfo, HhStats, IngestDense, SKE_HH_ID_BYTES, SKE_MEM_DEVICE,
+                   SKE_TP_BINS)
 from . import synthetic
 
 PASS_KINDS = 9  # SKE_PASS_KINDS (include/sketch.h)
@@ -86,6 +87,28 @@ def hh_list(ctx: Context, hid: int, cid: int, threshold: int, room: int | None =
              lens.ctypes.data_as(C.c_void_p), est.ctypes.data_as(C.c_void_p), room, C.byref(n), C.byref(complete))
     k = int(n.value)
     return [ids[i, :lens[i]].tobytes() for i in range(k)], est[:k].copy(), bool(complete.value)
+
+
+def hh_stats(ctx: Context, hid: int, cid: int, threshold: int = 0) -> dict:
+    """ske_hh_stats: the fields of ske_hh_stats_t as Python ints (``reserved``
+    left out) -- over the members of set ``hid`` whose current estimate in table
+    ``cid`` is at least ``threshold``."""
+    s = HhStats()
+    ctx.call("ske_hh_stats", int(hid), int(cid), int(threshold), C.byref(s))
+    return {k: int(getattr(s, k)) for k in ("n", "sum", "sq_lo", "sq_hi", "min", "max", "med_lo", "med_hi",
+                                            "complete")}
+
+
+def hh_select(ctx: Context, hid: int, cid: int, threshold: int, ranks) -> np.ndarray:
+    """ske_hh_select: the ``ranks[j]``-th smallest passing estimates (0-based),
+    at most SKE_HH_MAX_RANKS ranks a call; a rank at or above the number that
+    pass raises (SKE_EINVAL)."""
+    r = np.ascontiguousarray(ranks, dtype=np.uint64).reshape(-1)
+    out = np.zeros(r.size, np.uint32)
+    n = C.c_uint64(0)
+    ctx.call("ske_hh_select", int(hid), int(cid), int(threshold), r.ctypes.data_as(C.c_void_p), int(r.size),
+             out.ctypes.data_as(C.c_void_p), C.byref(n))
+    return out
 
 
 def tp_counts(ctx: Context, tid: int) -> np.ndarray:
@@ -383,6 +406,12 @@ class SketchEngine:
 
     def hh_list(self, hid: int, cid: int, threshold: int):
         return hh_list(self.ctx, hid, cid, threshold)
+
+    def hh_stats(self, hid: int, cid: int, threshold: int = 0) -> dict:
+        return hh_stats(self.ctx, hid, cid, threshold)
+
+    def hh_select(self, hid: int, cid: int, threshold: int, ranks) -> np.ndarray:
+        return hh_select(self.ctx, hid, cid, threshold, ranks)
 
     # ---- time profile: weekday x hour counters of the swipes' times
     def tp_init(self, tid: int):
