@@ -95,6 +95,8 @@ extern "C" {
 #define SKE_TP_BINS 168      /* weekday * 24 + hour, Monday = 0 */
 #define SKE_HLL_REGISTERS 16384
 #define SKE_HLL_DENSE_BYTES 12288
+#define SKE_HLL_DUMP_MAX_KEYS (1u << 18)   /* 2^18 * 12304 B < 2^32: u32 offsets suffice */
+#define SKE_HLL_DUMP_CARD 1                /* flags: write the cached cardinality */
 
 typedef struct ske_ctx ske_ctx;
 
@@ -233,6 +235,38 @@ int ske_hll_merge_groups_dev(ske_ctx *ctx, const uint32_t *slots, const uint32_t
                              uint32_t ngroups, uint8_t *dst_dev);
 /* estimator only: PFCOUNT of raw register arrays already on the device */
 int ske_hll_count_raw_dev(ske_ctx *ctx, const uint8_t *regs_dev, uint32_t nkeys, uint64_t *out);
+/* Many keys as Redis stores them (GET of an HLL key), encoded on the device:
+ * a 16-byte header ("HYLL", encoding 0 dense / 1 sparse, 3 zero bytes, 8
+ * cardinality bytes: cache-invalid, or with SKE_HLL_DUMP_CARD the key's PFCOUNT)
+ * and the canonical sparse payload (maximal runs) when every register is <= 32
+ * and it is at most sparse_max_bytes long (server.hll_sparse_max_bytes, 3000 in
+ * Redis), else the 12288-byte dense payload.  slots == NULL: keys 0..nkeys-1; a
+ * slot may repeat.  mem covers every array argument.  At most
+ * SKE_HLL_DUMP_MAX_KEYS keys a call (SKE_EINVAL); a slot outside the slab gives
+ * SKE_ERANGE and nothing is written.  Synchronous on the context stream.
+ *   ske_hll_dump_sizes: offs_out[nkeys+1], the byte offset of every key's
+ *     string, offs_out[nkeys] = total.  Writes no strings.
+ *   ske_hll_dump: the strings, back to back in out[0 .. total), and the same
+ *     offsets; cap < total -> SKE_EINVAL, out and offs_out untouched.
+ *   replaces: GET key on an HLL key, per key dump_hll */
+int ske_hll_dump_sizes(ske_ctx *ctx, const uint32_t *slots, uint32_t nkeys, uint32_t sparse_max_bytes,
+                       uint32_t *offs_out, int mem);
+int ske_hll_dump(ske_ctx *ctx, const uint32_t *slots, uint32_t nkeys, uint32_t sparse_max_bytes, int flags,
+                 uint8_t *out, uint64_t cap, uint32_t *offs_out, int mem);
+/* SET of nkeys HLL strings, decoded on the device: string i is
+ * blob[offs[i] .. offs[i+1]) (any byte alignment; offs never decreasing, else
+ * SKE_EINVAL), either encoding, canonical or not.  status_or_null[i] = 0
+ * loaded (the row of slots[i] is replaced), 1 not an HLL string (shorter than
+ * 16 bytes or another magic), 2 corrupted (a dense payload not 12288 bytes or
+ * a register above 51; sparse runs that do not end exactly at register 16384,
+ * an XZERO without its second byte; another encoding byte); the row of a key
+ * with a non-zero status is untouched, every other key of the call is loaded.
+ * Returns SKE_EBADHLL when any status is non-zero.  The slots must be distinct
+ * (with a repeated slot which string it ends up holding is unspecified);
+ * slots == NULL: keys 0..nkeys-1.  Limits, range check and mem as ske_hll_dump.
+ *   replaces: SET key <HYLL string>, per key load_hll */
+int ske_hll_load(ske_ctx *ctx, const uint32_t *slots, uint32_t nkeys, const uint8_t *blob,
+                 const uint32_t *offs, uint8_t *status_or_null, int mem);
 
 /* ---- Count-Min Sketch (RedisBloom src/cms.c) ----
  * A table of `depth` rows of `width` u32 counters (row-major) and a u64 count

@@ -61,6 +61,8 @@ SKE_MAX_TP = 256
 SKE_TP_BINS = 168
 HLL_REGISTERS = 16384
 HLL_DENSE_BYTES = 12288
+SKE_HLL_DUMP_MAX_KEYS = 1 << 18
+SKE_HLL_DUMP_CARD = 1
 
 
 class SketchLibError(RuntimeError):
@@ -162,6 +164,9 @@ SIGNATURES = {
     "ske_hll_slab": (C.c_int, [_CTX, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "ske_hll_merge_groups_dev": (C.c_int, [_CTX, _u32p, _u32p, C.c_uint32, _u8p]),
     "ske_hll_count_raw_dev": (C.c_int, [_CTX, _u8p, C.c_uint32, _u64p]),
+    "ske_hll_dump_sizes": (C.c_int, [_CTX, _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_int]),
+    "ske_hll_dump": (C.c_int, [_CTX, _u32p, C.c_uint32, C.c_uint32, C.c_int, _u8p, C.c_uint64, _u32p, C.c_int]),
+    "ske_hll_load": (C.c_int, [_CTX, _u32p, C.c_uint32, _u8p, _u32p, _u8p, C.c_int]),
     "ske_cms_dims_from_prob": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_uint32),
                                          C.POINTER(C.c_uint32)]),
     "ske_cms_init": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_uint32]),

@@ -1,5 +1,8 @@
 """The HyperLogLog half of ``SketchClient`` (csrc/sketch_api_hll.cpp): PFADD /
-PFCOUNT / PFMERGE over the register slab, and the keys as Redis strings."""
+PFCOUNT / PFMERGE over the register slab, and the keys as Redis strings: one
+key a call on the host (``dump_hll`` / ``load_hll``), many keys a call encoded
+and decoded on the device (``dump_hlls`` / ``load_hlls``, csrc/sketch_hll_fmt.hip),
+and a file of them (``save_hlls`` / ``restore_hlls``)."""
 from __future__ import annotations
 
 from typing import Sequence
@@ -7,10 +10,17 @@ from typing import Sequence
 import numpy as np
 
 from . import formats
-from ._lib import SKE_MEM_HOST, HLL_DENSE_BYTES, HLL_REGISTERS, ptr as _ptr
+from ._lib import (SKE_EBADHLL, SKE_HLL_DUMP_CARD, SKE_HLL_DUMP_MAX_KEYS, SKE_MEM_HOST, HLL_DENSE_BYTES,
+                   HLL_REGISTERS, SketchLibError, ptr as _ptr)
 from .commands import arity_error
 from .encoding import encode, pack
 from .exceptions import DataError, ResponseError
+from .keyspace import redis_glob
+
+# a string longer than the header and the longest valid sparse payload (16384
+# XZERO opcodes of run 1) cannot be valid: load_hlls refuses it without a copy
+_HLL_STRING_MAX = formats.HLL_HDR + 2 * HLL_REGISTERS
+_LOAD_CALL_BYTES = 1 << 31  # blob bytes per ske_hll_load call (u32 offsets)
 
 
 class HllMixin:
@@ -166,6 +176,166 @@ class HllMixin:
         if k in self.keys.kind and self.keys.kind[k] != "hll":
             self.keys.drop(k)  # SET replaces a key of any type
         self.hll_load_registers(k, regs)
+
+    # ------------------------------------------------------------ many keys a call
+    def dump_hlls(self, names: Sequence, with_card: bool = False, sparse_max_bytes: int = 3000,
+                  chunk_keys: int | None = None) -> list:
+        """``dump_hll`` of every name, encoded on the device: entry i is the
+        key as Redis stores it, None for a missing key; a key of another type
+        raises before anything runs.  ``with_card``: the header caches the
+        key's PFCOUNT (``formats.cached_card``) instead of the invalid mark.
+        ``chunk_keys``: keys per ske_hll_dump call (default the ABI's most)."""
+        keys = [encode(n) for n in names]
+        have = [i for i, k in enumerate(keys) if self.keys.expect(k, "hll")]
+        out: list = [None] * len(keys)
+        chunk = int(chunk_keys) if chunk_keys else SKE_HLL_DUMP_MAX_KEYS
+        if chunk < 1:
+            raise ValueError("chunk_keys must be positive")
+        for c0 in range(0, len(have), chunk):
+            part = have[c0:c0 + chunk]
+            slots = np.asarray([self.keys.slot[keys[i]] for i in part], dtype=np.uint32)
+            blob, offs = self.dump_slots(slots, with_card, sparse_max_bytes)
+            for j, i in enumerate(part):
+                out[i] = blob[int(offs[j]):int(offs[j + 1])].tobytes()
+        return out
+
+    def dump_slots(self, slots: np.ndarray, with_card: bool = False,
+                   sparse_max_bytes: int = 3000) -> tuple[np.ndarray, np.ndarray]:
+        """The strings of up to SKE_HLL_DUMP_MAX_KEYS slab slots as one blob
+        (u8) and their offsets (u32, one more than slots): the sizes first,
+        then the strings into a buffer of exactly that size."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        offs = np.zeros(slots.size + 1, np.uint32)
+        self.ctx.call("ske_hll_dump_sizes", _ptr(slots), slots.size, int(sparse_max_bytes), _ptr(offs),
+                      SKE_MEM_HOST)
+        blob = np.zeros(int(offs[-1]), np.uint8)
+        self.ctx.call("ske_hll_dump", _ptr(slots), slots.size, int(sparse_max_bytes),
+                      SKE_HLL_DUMP_CARD if with_card else 0, _ptr(blob), blob.size, _ptr(offs), SKE_MEM_HOST)
+        return blob, offs
+
+    @staticmethod
+    def _raise_bad_hll(value: bytes):
+        """load_hll's error for a string the device refused."""
+        formats.decode_hll(value)  # WRONGTYPE / INVALIDOBJ as load_hll raises them
+        # a dense register above 51: decode_hll lets it pass, ske_hll_import_raw does not
+        raise SketchLibError(SKE_EBADHLL, formats.INVALIDOBJ)
+
+    @staticmethod
+    def _host_refuses(value: bytes) -> bool:
+        try:
+            return int(formats.decode_hll(value).max(initial=0)) > 51
+        except ResponseError:
+            return True
+
+    def load_hlls(self, pairs, chunk_keys: int | None = None) -> None:
+        """``load_hll`` of every (name, string) pair in order, decoded on the
+        device: new keys get slots, a key of another type is replaced, a name
+        that repeats ends up with its last good string.  A string that is not a
+        valid HLL string raises ``load_hll``'s error for the first such pair --
+        after every good pair is in; a name with no good string is not created
+        (and a key it names stays as it was)."""
+        items = [(encode(n), bytes(v)) for n, v in pairs]
+        chunk = int(chunk_keys) if chunk_keys else SKE_HLL_DUMP_MAX_KEYS
+        if chunk < 1:
+            raise ValueError("chunk_keys must be positive")
+        first_bad = None
+        pending: dict[bytes, list[int]] = {}  # name -> its pairs, in order
+        for i, (k, _) in enumerate(items):
+            pending.setdefault(k, []).append(i)
+        while pending:
+            # every name's last pair not yet refused
+            batch = []
+            for k, idxs in pending.items():
+                v = items[idxs[-1]][1]
+                kind = self.keys.kind.get(k)
+                if len(v) > _HLL_STRING_MAX or (kind not in (None, "hll") and self._host_refuses(v)):
+                    batch.append((k, None))  # refused here: too long, or it must not replace the other key
+                    continue
+                if kind not in (None, "hll"):
+                    self.keys.drop(k)  # SET replaces a key of any type
+                batch.append((k, v))
+            bad = [k for k, v in batch if v is None]
+            send = [(k, v) for k, v in batch if v is not None]
+            c0 = 0
+            while c0 < len(send):
+                c1, nbytes = c0, 0
+                while c1 < len(send) and c1 - c0 < chunk and nbytes + len(send[c1][1]) <= _LOAD_CALL_BYTES:
+                    nbytes += len(send[c1][1])
+                    c1 += 1
+                bad += self._load_batch(send[c0:c1])
+                c0 = c1
+            nxt = {}
+            for k in bad:
+                idxs = pending[k]
+                i = idxs.pop()
+                first_bad = i if first_bad is None else min(first_bad, i)
+                if idxs:
+                    nxt[k] = idxs
+            pending = nxt
+        if first_bad is not None:
+            self._raise_bad_hll(items[first_bad][1])
+
+    def _load_batch(self, batch: list) -> list:
+        """One ske_hll_load of (name, string) pairs with distinct names; the
+        names whose string the device refused (a name it created for them is
+        taken back)."""
+        created = []
+        slots = np.zeros(len(batch), np.uint32)
+        for j, (k, _) in enumerate(batch):
+            if k in self.keys.slot:
+                slots[j] = self.keys.slot[k]
+            else:
+                slots[j] = self.keys.new_slot(k)
+                created.append(k)
+        offs = np.zeros(len(batch) + 1, np.uint32)
+        np.cumsum([len(v) for _, v in batch], out=offs[1:])
+        blob = np.frombuffer(b"".join(v for _, v in batch), dtype=np.uint8)
+        status = np.zeros(len(batch), np.uint8)
+        try:
+            self.ctx.call("ske_hll_load", _ptr(slots), len(batch), _ptr(blob) if blob.size else None, _ptr(offs),
+                          _ptr(status), SKE_MEM_HOST)
+        except SketchLibError as e:
+            if e.code != SKE_EBADHLL:
+                for k in created:
+                    self.keys.release_unused_slot(k)
+                raise
+        bad = [batch[j][0] for j in np.flatnonzero(status)]
+        made = set(created)
+        for k in bad:
+            if k in made:
+                self.keys.release_unused_slot(k)  # its row was never written
+        return bad
+
+    def save_hlls(self, path, match="*") -> int:
+        """Every HLL key whose name matches (Redis' glob) into one ``.npz``
+        file at ``path``: the packed key names and their offsets, the keys'
+        Redis strings as one blob and their offsets.  The container is this
+        project's own; the strings are Redis'.  Returns the number of keys."""
+        pat = encode(match)
+        keys = sorted(k for k, kind in self.keys.kind.items()
+                      if kind == "hll" and (pat == b"*" or redis_glob(pat, k)))
+        blobs, offs, total = [], [np.zeros(1, np.uint64)], 0
+        for c0 in range(0, len(keys), SKE_HLL_DUMP_MAX_KEYS):
+            slots = np.asarray([self.keys.slot[k] for k in keys[c0:c0 + SKE_HLL_DUMP_MAX_KEYS]], dtype=np.uint32)
+            blob, o = self.dump_slots(slots)
+            blobs.append(blob)
+            offs.append(o[1:].astype(np.uint64) + np.uint64(total))
+            total += int(o[-1])
+        name_offs = np.zeros(len(keys) + 1, np.uint64)
+        np.cumsum([len(k) for k in keys], out=name_offs[1:])
+        with open(path, "wb") as f:
+            np.savez(f, names=np.frombuffer(b"".join(keys), dtype=np.uint8), name_offs=name_offs,
+                     offs=np.concatenate(offs), blob=np.concatenate(blobs) if blobs else np.zeros(0, np.uint8))
+        return len(keys)
+
+    def restore_hlls(self, path) -> int:
+        """``load_hlls`` of every key of a ``save_hlls`` file; the number of keys."""
+        with np.load(path) as z:
+            names, name_offs, offs, blob = z["names"].tobytes(), z["name_offs"], z["offs"], z["blob"].tobytes()
+        n = len(name_offs) - 1
+        self.load_hlls((names[int(name_offs[i]):int(name_offs[i + 1])], blob[int(offs[i]):int(offs[i + 1])])
+                       for i in range(n))
+        return n
 
     def key_slot(self, name, create: bool = True) -> int:
         """Slot of an HLL key (creating it when asked) for batched calls."""

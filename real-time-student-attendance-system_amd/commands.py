@@ -29,6 +29,21 @@ def _get(c, a):
     return c.dump_hll(k)
 
 
+def _mget(c, a):
+    """GET's rule per key, over the bulk dump; a missing or non-string key
+    answers None, as Redis' MGET does."""
+    keys = [encode(k) for k in a]
+    hll = [k for k in keys if c.keys.type_of(k) == "hll"]
+    got = dict(zip(hll, c.dump_hlls(hll)))
+    return [got.get(k) for k in keys]
+
+
+def _mset(c, a):
+    if len(a) % 2:
+        raise arity_error("mset")
+    c.load_hlls([(a[i], encode(a[i + 1])) for i in range(0, len(a), 2)])
+
+
 def _then_ok(method):
     """A command whose facade method replies True (or nothing) and Redis OK."""
     def handler(c, a):
@@ -61,6 +76,8 @@ COMMANDS = {
     "PFMERGE": (1, None, _then_ok(lambda c, a: c.pfmerge(*a))),
     "GET": (1, 1, _get),
     "SET": (2, 2, _then_ok(lambda c, a: c.load_hll(a[0], encode(a[1])))),
+    "MGET": (1, None, _mget),
+    "MSET": (2, None, _then_ok(_mset)),
     "DEL": (1, None, lambda c, a: c.delete(*a)),
     "EXISTS": (1, None, lambda c, a: c.exists(*a)),
     "TYPE": (1, 1, lambda c, a: c.type(a[0])),

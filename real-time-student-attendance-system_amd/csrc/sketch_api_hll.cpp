@@ -1,5 +1,6 @@
 // sketch_api_hll.cpp -- libsketch C-ABI (include/sketch.h): the HLL register
-// slab, PFADD, PFCOUNT, PFMERGE, export / import.
+// slab, PFADD, PFCOUNT, PFMERGE, export / import, and many keys as Redis
+// strings (ske_hll_dump*, ske_hll_load over sketch_hll_fmt.hip).
 //
 // The PFCOUNT estimator's m*tau(.) / m*sigma(.) tables (src/hyperloglog.c
 // hllTau / hllSigma) are built here with the same libm calls as Redis.
@@ -87,6 +88,42 @@ static int check_slots_dev(ske_ctx *c, const uint32_t *slots, uint64_t n) {
     HIPCHK(c, hipMemcpyAsync(&mx, d, 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     return mx >= c->nslots ? SKE_ERANGE : SKE_OK;
+}
+
+// the slot list of a bulk call (nullptr: keys 0 .. nkeys - 1) in range of the
+// slab, and on the device
+static int bulk_slots(ske_ctx *c, const uint32_t *slots, uint32_t nkeys, int mem, const uint32_t **ds) {
+    *ds = nullptr;
+    if (!slots) return nkeys > c->nslots ? SKE_ERANGE : SKE_OK;
+    int rc = mem == SKE_MEM_DEVICE ? check_slots_dev(c, slots, nkeys) : check_slots_host(c, slots, nkeys);
+    if (rc) return rc;
+    return stage_u32(c, slots, nkeys, mem, kStgList, ds);
+}
+
+// The string offsets of the listed keys (device, nkeys + 1 entries, in the
+// context scratch) and their last entry, the total.  Returns after a stream
+// synchronise.
+static int dump_offsets(ske_ctx *c, const uint32_t *ds, uint32_t nkeys, uint32_t smb, uint32_t **doffs,
+                        uint32_t *total) {
+    hipError_t e = hipSuccess;
+    uint32_t *sizes = (uint32_t *)scratch_get(c->scratch, kScrHllFmtSize, size_t(nkeys) * 4 + 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    uint32_t *offs = (uint32_t *)scratch_get(c->scratch, kScrHllFmtOffs, size_t(nkeys) * 4 + 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    HIPCHK(c, hipMemsetAsync(offs, 0, 4, c->st));
+    HIPCHK(c, launch_hll_fmt_sizes(c->regs, ds, nkeys, c->nslots, smb, sizes, c->cus, c->st));
+    HIPCHK(c, scan_inclusive_u32(c->scratch, sizes, offs + 1, nkeys, c->st));
+    HIPCHK(c, hipMemcpyAsync(total, offs + nkeys, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    *doffs = offs;
+    return SKE_OK;
+}
+
+static int copy_out(ske_ctx *c, void *dst, const void *dev, size_t bytes, int mem) {
+    if (bytes == 0) return SKE_OK;
+    HIPCHK(c, hipMemcpyAsync(dst, dev, bytes, mem == SKE_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                             c->st));
+    return SKE_OK;
 }
 
 static int pfmerge_impl(ske_ctx *c, uint32_t dst, const uint32_t *srcs, uint32_t n, int mem) {
@@ -323,6 +360,91 @@ int ske_hll_import_raw(ske_ctx *c, uint32_t slot, const uint8_t *in) {
                              hipMemcpyHostToDevice, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     return SKE_OK;
+}
+
+int ske_hll_dump_sizes(ske_ctx *c, const uint32_t *slots, uint32_t nkeys, uint32_t sparse_max_bytes,
+                       uint32_t *offs_out, int mem) {
+    if (!c || !offs_out || nkeys > SKE_HLL_DUMP_MAX_KEYS) return SKE_EINVAL;
+    const uint32_t *ds;
+    int rc = bulk_slots(c, slots, nkeys, mem, &ds);
+    if (rc) return rc;
+    uint32_t *doffs, total = 0;
+    rc = dump_offsets(c, ds, nkeys, sparse_max_bytes, &doffs, &total);
+    if (rc) return rc;
+    rc = copy_out(c, offs_out, doffs, size_t(nkeys) * 4 + 4, mem);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SKE_OK;
+}
+
+int ske_hll_dump(ske_ctx *c, const uint32_t *slots, uint32_t nkeys, uint32_t sparse_max_bytes, int flags,
+                 uint8_t *out, uint64_t cap, uint32_t *offs_out, int mem) {
+    if (!c || !offs_out || nkeys > SKE_HLL_DUMP_MAX_KEYS || (flags & ~SKE_HLL_DUMP_CARD)) return SKE_EINVAL;
+    const uint32_t *ds;
+    int rc = bulk_slots(c, slots, nkeys, mem, &ds);
+    if (rc) return rc;
+    uint32_t *doffs, total = 0;
+    rc = dump_offsets(c, ds, nkeys, sparse_max_bytes, &doffs, &total);
+    if (rc) return rc;
+    if (cap < total || (total && !out)) return SKE_EINVAL;
+    uint8_t *dout = out;
+    if (mem != SKE_MEM_DEVICE && total) {
+        dout = (uint8_t *)stage_buf(c, kStgHllFmtBlob, total, &rc);
+        if (rc) return rc;
+    }
+    const uint64_t *card = nullptr;
+    if ((flags & SKE_HLL_DUMP_CARD) && nkeys) {
+        rc = ensure_tables(c);
+        if (rc) return rc;
+        hipError_t e = hipSuccess;
+        uint64_t *dc = (uint64_t *)scratch_get(c->scratch, kScrHllFmtCard, size_t(nkeys) * 8, &e);
+        if (e != hipSuccess) return scratch_error(c, e);
+        HIPCHK(c, launch_pfcount(c->regs, ds, nullptr, nkeys, c->tau, c->sig, dc, c->cus, c->st));
+        card = dc;
+    }
+    HIPCHK(c, launch_hll_fmt_dump(c->regs, ds, nkeys, c->nslots, sparse_max_bytes, card, doffs, dout, c->cus, c->st));
+    if (mem != SKE_MEM_DEVICE) {
+        rc = copy_out(c, out, dout, total, mem);
+        if (rc) return rc;
+    }
+    rc = copy_out(c, offs_out, doffs, size_t(nkeys) * 4 + 4, mem);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SKE_OK;
+}
+
+int ske_hll_load(ske_ctx *c, const uint32_t *slots, uint32_t nkeys, const uint8_t *blob, const uint32_t *offs,
+                 uint8_t *status, int mem) {
+    if (!c || !offs || nkeys > SKE_HLL_DUMP_MAX_KEYS) return SKE_EINVAL;
+    if (nkeys == 0) return SKE_OK;
+    const uint32_t *ds;
+    int rc = bulk_slots(c, slots, nkeys, mem, &ds);
+    if (rc) return rc;
+    unsigned int *flag = (unsigned int *)stage_buf(c, kStgHllFmtFlag, 4, &rc);
+    if (rc) return rc;
+    unsigned int word = 0;
+    Staged s;
+    if (mem == SKE_MEM_DEVICE) {  // host offsets are checked as stage_items copies them
+        if (!blob) return SKE_EINVAL;
+        HIPCHK(c, hipMemsetAsync(flag, 0, 4, c->st));
+        HIPCHK(c, launch_hll_fmt_offs_check(offs, nkeys, flag, c->cus, c->st));
+        HIPCHK(c, hipMemcpyAsync(&word, flag, 4, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        if (word) return SKE_EINVAL;
+    }
+    rc = stage_items(c, blob, offs, nkeys, mem, &s);
+    if (rc) return rc;
+    uint8_t *dstat = status;
+    if (status && mem != SKE_MEM_DEVICE) {
+        dstat = (uint8_t *)stage_buf(c, kStgHllFmtStatus, nkeys, &rc);
+        if (rc) return rc;
+    }
+    HIPCHK(c, hipMemsetAsync(flag, 0, 4, c->st));
+    HIPCHK(c, launch_hll_fmt_load(c->regs, ds, nkeys, c->nslots, s.bytes, s.offs, dstat, flag, c->cus, c->st));
+    if (status && mem != SKE_MEM_DEVICE) HIPCHK(c, hipMemcpyAsync(status, dstat, nkeys, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(&word, flag, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return word ? SKE_EBADHLL : SKE_OK;
 }
 
 int ske_hll_slab(ske_ctx *c, void **p, uint64_t *bytes) {

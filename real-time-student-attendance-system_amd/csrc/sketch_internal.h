@@ -308,6 +308,26 @@ constexpr unsigned kTpMaxGrid = 4096;
 // 1: one LDS atomic per lane, always.  grid: workgroups (at most kTpMaxGrid; fewer for a small n)
 hipError_t launch_tp_add(const TpArgs &A, int form, unsigned grid, hipStream_t st);
 
+// sketch_hll_fmt.hip -- HLL keys as Redis "HYLL" strings, one key per workgroup
+// (DESIGN.md section 14); the opcode rules are sketch_hll_fmt.h's
+// sizes[i] = length of key i's string (slots == nullptr: keys 0 .. nkeys - 1);
+// smb: the longest sparse payload before a key is written dense
+hipError_t launch_hll_fmt_sizes(const uint8_t *regs, const uint32_t *slots, uint32_t nkeys, uint32_t nslots,
+                                uint32_t smb, uint32_t *sizes, int cus, hipStream_t st);
+// string i at out + offs[i], offs the exclusive scan of the sizes (nkeys + 1
+// entries); card (may be null): the cardinality the header caches, per key
+hipError_t launch_hll_fmt_dump(const uint8_t *regs, const uint32_t *slots, uint32_t nkeys, uint32_t nslots,
+                               uint32_t smb, const uint64_t *card, const uint32_t *offs, uint8_t *out, int cus,
+                               hipStream_t st);
+// row of slots[i] = the registers of the string blob[offs[i] .. offs[i + 1])
+// when it is valid; status (may be null): kHllFmtOk / NotHll / Corrupt per key;
+// *anybad (zeroed by the caller) |= 1 when a string was not loaded
+hipError_t launch_hll_fmt_load(uint8_t *regs, const uint32_t *slots, uint32_t nkeys, uint32_t nslots,
+                               const uint8_t *blob, const uint32_t *offs, uint8_t *status, unsigned int *anybad,
+                               int cus, hipStream_t st);
+// *bad (zeroed by the caller) |= 1 when offs[0 .. n] decreases somewhere
+hipError_t launch_hll_fmt_offs_check(const uint32_t *offs, uint32_t n, unsigned int *bad, int cus, hipStream_t st);
+
 // sketch_order.hip -- order-exact paths (replies that depend on item order)
 struct Scratch;  // growable device scratch, owned by the context
 constexpr int kScratchSlots = 48;
@@ -336,7 +356,8 @@ enum ScratchSlot : int {
     kScrSortTmp,       //   rocprim radix sort temporary,
     kScrScanKeyTmp,    //   rocprim scan-by-key temporary
     kScrScanTmp,       // scan_inclusive_u32's rocprim temporary: ske_bf_madd, ske_keytab_lookup,
-                       // ske_ingest_swipes, ske_ingest_dense (synchronous calls, never at once)
+                       // ske_ingest_swipes, ske_ingest_dense, ske_hll_dump_sizes, ske_hll_dump
+                       // (synchronous calls, never at once)
     kScrBfHa,          // ske_bf_madd: item hashes a,
     kScrBfHb,          //   hashes b,
     kScrBfState,       //   candidate state,
@@ -354,6 +375,9 @@ enum ScratchSlot : int {
     kScrInOffs,        //   their offsets,
     kScrInKslot,       //   their slots,
     kScrInKvalid,      //   K1's answers
+    kScrHllFmtSize,    // ske_hll_dump_sizes, ske_hll_dump (sketch_api_hll.cpp): a string length per key,
+    kScrHllFmtOffs,    //   their exclusive scan (nkeys + 1 offsets),
+    kScrHllFmtCard,    //   ske_hll_dump with SKE_HLL_DUMP_CARD: a PFCOUNT per key
     // -- xr
     kScrXr,            // launch_k1: the XCD-partitioned K1's state (sketch_xr.hip)
     kScrPartRec,       // part_scratch (sketch_part.hip): probe records,
@@ -381,13 +405,13 @@ static_assert(kScratchSlotCount <= kScratchSlots, "Scratch holds kScratchSlots s
 // The context's staging buffers (ske_ctx::stg) by use; every user is a
 // synchronous call on the context stream.
 enum StageSlot : int {
-    kStgBytes,     // item bytes (stage_items; the fixed-width ids of ske_swipes_fixed*)
-    kStgOffs,      // item offsets (stage_items)
+    kStgBytes,     // item bytes (stage_items; the fixed-width ids of ske_swipes_fixed*; ske_hll_load's blob)
+    kStgOffs,      // item offsets (stage_items; ske_hll_load's string offsets)
     kStgSlots,     // a slot per item
     kStgOut,       // per-item replies on their way to the host (answers, changed flags, packed bits)
     kStgAnswers,   // ske_swipes_fixed_bits: answer bytes before packing
     kStgReply,     // small replies: PFCOUNT results, a histogram, a dense export
-    kStgList,      // a slot list (PFCOUNT / PFMERGE) or key hashes (ske_keytab_insert)
+    kStgList,      // a slot list (PFCOUNT / PFMERGE / ske_hll_dump* / ske_hll_load) or key hashes (ske_keytab_insert)
     kStgList2,     // group offsets (PFCOUNT) or key slots (ske_keytab_insert)
     kStgCheck,     // the device slot-range check word (check_slots_dev)
     kStgCmsIncr,   // ske_cms_incrby: an increment per item
@@ -399,6 +423,9 @@ enum StageSlot : int {
     kStgHhEst,     //   estimates
     kStgHhStat,    // ske_hh_stats / ske_hh_select: the accumulators, the rank state and the histograms (HhStatDev),
     kStgHhSelEst,  //   the passing estimates, compacted (4 bytes per slot of the set)
+    kStgHllFmtBlob,    // ske_hll_dump: the strings on their way to the host
+    kStgHllFmtStatus,  // ske_hll_load: a status byte per key on its way to the host
+    kStgHllFmtFlag,    // ske_hll_load: the offsets-decrease word, then the any-string-refused word
     kStageSlotCount
 };
 

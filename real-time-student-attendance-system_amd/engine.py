@@ -13,8 +13,8 @@ import gc
 
 import numpy as np
 
-from ._lib import (CmsInfo, Context, GenParams, HhInfo, HhStats, IngestDense, SKE_HH_ID_BYTES, SKE_MEM_DEVICE,
-                   SKE_TP_BINS)
+from ._lib import (CmsInfo, Context, GenParams, HhInfo, HhStats, IngestDense, SKE_HH_ID_BYTES, SKE_HLL_DUMP_CARD,
+                   SKE_MEM_DEVICE, SKE_TP_BINS)
 from . import synthetic
 
 PASS_KINDS = 9  # SKE_PASS_KINDS (include/sketch.h)
@@ -531,6 +531,31 @@ class SketchEngine:
             self.ctx.call("ske_hll_pfcount_each", s.ctypes.data_as(C.c_void_p), s.size,
                           out.ctypes.data_as(C.c_void_p), 0)
         return out
+
+    # ---- HLL keys as Redis strings, many a call, every array on the device
+    def hll_dump_sizes(self, slots: DeviceBuffer | None, nkeys: int, offs: DeviceBuffer,
+                       sparse_max_bytes: int = 3000):
+        """ske_hll_dump_sizes: ``offs`` (nkeys + 1 u32) receives the byte offset
+        of every listed key's "HYLL" string, the last entry the total.
+        ``slots`` None: keys 0 .. nkeys - 1."""
+        self.ctx.call("ske_hll_dump_sizes", C.c_void_p(slots.ptr) if slots else None, int(nkeys),
+                      int(sparse_max_bytes), C.c_void_p(offs.ptr), SKE_MEM_DEVICE)
+
+    def hll_dump(self, slots: DeviceBuffer | None, nkeys: int, out: DeviceBuffer, offs: DeviceBuffer,
+                 sparse_max_bytes: int = 3000, with_card: bool = False):
+        """ske_hll_dump: the strings back to back into ``out`` (its size is
+        the capacity), their offsets into ``offs``."""
+        self.ctx.call("ske_hll_dump", C.c_void_p(slots.ptr) if slots else None, int(nkeys), int(sparse_max_bytes),
+                      SKE_HLL_DUMP_CARD if with_card else 0, C.c_void_p(out.ptr), int(out.nbytes),
+                      C.c_void_p(offs.ptr), SKE_MEM_DEVICE)
+
+    def hll_load(self, slots: DeviceBuffer | None, nkeys: int, blob: DeviceBuffer, offs: DeviceBuffer,
+                 status: DeviceBuffer | None = None):
+        """ske_hll_load: SET of the nkeys strings ``blob[offs[i] .. offs[i + 1])``
+        into the (distinct) slots; raises SKE_EBADHLL after loading the good
+        ones when a string is refused (``status``: a byte per key)."""
+        self.ctx.call("ske_hll_load", C.c_void_p(slots.ptr) if slots else None, int(nkeys), C.c_void_p(blob.ptr),
+                      C.c_void_p(offs.ptr), C.c_void_p(status.ptr) if status else None, SKE_MEM_DEVICE)
 
     def bloom_bits(self, fid: int, link: int, nbytes: int) -> np.ndarray:
         out = np.zeros(nbytes, np.uint8)
