@@ -502,8 +502,6 @@ int ske_set_option(ske_ctx *c, const char *name, int64_t value) {
         {"seg_klog", 0, 3, [](ske_ctx *x, int64_t v) { x->seg.klog = int(v); }},
         // segmented PFADD: 2^b1 level-1 buckets, -1 auto
         {"seg_b1", -1, 9, [](ske_ctx *x, int64_t v) { x->seg.b1 = int(v); }},
-        // pass A's records in the group layout: -1 auto, 0 per-tile runs, 1 on
-        {"rec_groups", -1, 1, [](ske_ctx *x, int64_t v) { x->seg.rec_groups = int(v); }},
         // blocks of the short-id LDS K1 (0: one per CU)
         {"k1_grid", 0, 65535, [](ske_ctx *x, int64_t v) { x->k1_grid = int(v); }},
         // 0: many-batch calls launch K1 per batch

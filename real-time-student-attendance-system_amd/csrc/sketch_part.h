@@ -13,10 +13,8 @@ namespace ske {
 constexpr uint32_t kPSub = 1u << 26;                // swipes per sub-batch (passes A-B-C), at most
 constexpr uint32_t kPbGroup = 8;                    // tiles a pass-B wave reads at once
 constexpr uint32_t kPbLanes = 64 / kPbGroup;        // lanes per tile run
-constexpr uint32_t kPTileLog = 10;                  // swipes per tile = 1 << kPTileLog
-// swipes per tile of the fail-list chains (one link, k = 11: C3 / C5's
-// filter), as of every other chain
-constexpr uint32_t kTileFl = 1u << kPTileLog;
+constexpr uint32_t kPTileLog = 10;
+constexpr uint32_t kPTile = 1u << kPTileLog;        // swipes per tile, every chain's
 
 struct PartLink {
     const uint8_t *bf;
@@ -43,10 +41,6 @@ struct PartArgs {
     uint32_t fixed_w, n, stride, ntiles, nslices, nlinks, ksum, nslots, fail_stride, off_stride;
     uint16_t *flist;       // [nunits][fl_stride][kPbLanes] fail lists (pass B -> pass C), or nullptr
     uint32_t nunits, fl_stride;
-    // group layout (gcap != 0; k_part_a3 / k_part_b<2, 4, true, true>): the
-    // runs of a unit over a group of 8 tiles adjacent in rec[group][unit][gcap],
-    // a run that does not fit at its tile's place in rec[govf + tile * stride]
-    uint32_t gcap, govf;
     PartLink link[kPMaxLinks];
 };
 
@@ -65,8 +59,8 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // is placement for speed only: every tile of a group is handled by exactly one
 // block of the group, whichever XCD it runs on.
 constexpr uint32_t kPGroups = 8;
-// (group edges on multiples of 8 tiles: pass B's rounds and the group layout's
-// 8-tile groups never straddle two XCD groups)
+// (group edges on multiples of 8 tiles: pass B's rounds of 8 tiles never
+// straddle two XCD groups)
 __device__ __forceinline__ void part_group(uint32_t ntiles, uint32_t x, uint32_t &t0, uint32_t &t1) {
     t0 = uint32_t(uint64_t(ntiles) * x / kPGroups) & ~7u;
     t1 = x + 1 == kPGroups ? ntiles : uint32_t(uint64_t(ntiles) * (x + 1) / kPGroups) & ~7u;
@@ -161,7 +155,7 @@ __device__ __forceinline__ void part_reg_max(uint32_t *w, uint32_t sh, uint32_t 
 }
 
 constexpr uint32_t kSegRunTiles = kPbGroup;                 // tiles per level-1 run
-constexpr uint32_t kSegRunSw = kSegRunTiles * kTileFl;      // 8192 swipes
+constexpr uint32_t kSegRunSw = kSegRunTiles * kPTile;       // 8192 swipes
 constexpr uint32_t kSegMaxB1 = 512;                         // level-1 buckets
 constexpr uint32_t kSegMaxWpb = 512;                        // windows per bucket
 // (kSegChunk, 8192 records per level-2 chunk: sketch_seg_plan.h)

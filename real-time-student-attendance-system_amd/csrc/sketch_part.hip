@@ -77,17 +77,22 @@
 //     (profiles/r05_ab_seg_slice.txt), two records per thread at klog 1 (spills,
 //     profiles/r06_ab_seg_e_rpt.txt) and slices of 8 k to 128 k records (0.930
 //     -> 0.891 ms for 32 k << klog, profiles/r05_ab_seg_slice.txt).
+// Round 19 removed the last form kept behind an option after losing its A/B:
+//   * pass A's group layout (a slice unit's runs of 8 consecutive tiles
+//     adjacent in a (group, unit) region, runs that do not fit in overflow
+//     rows; taken on request only): pass B 0.194-0.195 -> 0.182-0.183 ms but
+//     pass A 0.225-0.228 -> 0.380-0.388 ms per 16 M sub-batch, a net +0.14 ms
+//     (profiles/r05_ab_rec_groups.txt; DESIGN.md §3 keeps the table).
 //
 // Placement of blocks on XCDs is a speed matter only; every (tile, slice) run
 // is read by exactly one block, and fail marks are only ever set.
 #include <algorithm>
-#include <cmath>
 
 #include "sketch_part.h"
 
 namespace ske {
 
-constexpr uint32_t kPaBlock = 1024;
+constexpr uint32_t kPaBlock = kPTile;         // k_part_a: one thread per swipe of a tile
 constexpr uint32_t kPbBlock = 1024;
 constexpr uint32_t kPcBlock = 256;            // k_part_c (fail bytes)
 constexpr uint32_t kPSliceMask = kPSliceBits - 1;
@@ -168,7 +173,7 @@ __device__ __forceinline__ void part_hash3(const uint8_t *bytes, const PartId &d
 // k_part_a2 below.
 template <int KM>
 __global__ void __launch_bounds__(kPaBlock, KM <= 11 ? 8 : 4) k_part_a(const PartArgs A) {
-    __shared__ __attribute__((aligned(16))) uint32_t srec[kPaBlock * KM];
+    __shared__ __attribute__((aligned(16))) uint32_t srec[kPTile * KM];
     // slice histogram, then run starts; two buffers used by alternate tiles,
     // so the one the next tile counts into is cleared while this tile still
     // reads its own (four barriers per tile)
@@ -181,7 +186,7 @@ __global__ void __launch_bounds__(kPaBlock, KM <= 11 ? 8 : 4) k_part_a(const Par
     // the next tile's ids are loaded while this tile sorts: its offsets at the
     // top of the iteration, its id words after the scan
     auto offsets = [&](uint32_t t, uint32_t &b, uint32_t &e) {
-        const uint32_t i = t * kPaBlock + tid;
+        const uint32_t i = t * kPTile + tid;
         const uint32_t ic = i < A.n ? i : A.n - 1;
         b = A.offs ? A.offs[ic] : ic * A.fixed_w;
         e = A.offs ? A.offs[ic + 1] : b + A.fixed_w;
@@ -203,7 +208,7 @@ __global__ void __launch_bounds__(kPaBlock, KM <= 11 ? 8 : 4) k_part_a(const Par
         const uint32_t tn = t + tstep < gt1 ? t + tstep : t;
         offsets(tn, nb_, ne_);
         {
-            const uint32_t i = t * kPaBlock + tid;
+            const uint32_t i = t * kPTile + tid;
             const bool act = i < A.n;
             uint64_t ha, hb, hh;
             part_hash3(A.bytes, it, ha, hb, hh);
@@ -326,7 +331,7 @@ __global__ void __launch_bounds__(kPaBlock, KM <= 11 ? 8 : 4) k_part_a(const Par
 //   2  after the wave sums: swsum is complete before the block prefix, and
 //      every thread has read its counts before barrier 3's writers;
 //   3  after the scanned starts are written: placement reads only scanned
-//      counters, and swsum / stot / dmap are read before the next tile
+//      counters, and swsum / stot are read before the next tile
 //      rewrites them (its barriers 1 and 2 come first);
 //   4  after the placement: srec is complete before the copy-out reads it.
 //      The other parity's counters are cleared between 3 and 4 -- their last
@@ -334,26 +339,19 @@ __global__ void __launch_bounds__(kPaBlock, KM <= 11 ? 8 : 4) k_part_a(const Par
 //      tile's barrier 4 -- so the next tile counts on clear counters right
 //      after barrier 4 while this parity's scanned values are left alone
 //      until the tile after next's clearing.
-// GL: the group layout (PartArgs::gcap).  A block takes whole groups of 8
-// consecutive tiles, one tile after the other, and keeps each of its units'
-// place in the group's region in a register; every run starts on a 16-B
-// piece (padded to 4 records in LDS and in the region), so the copy-out stays
-// one 16-B store per piece, to the place an LDS map gives the piece's unit.
-template <int KM, uint32_t kCnt, bool GL = false>
+template <int KM, uint32_t kCnt>
 __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two blocks per CU
     constexpr uint32_t kT = 512;
-    constexpr uint32_t kU = kTileFl / kT, kTile = kTileFl;
+    constexpr uint32_t kU = kPTile / kT;
     constexpr uint32_t kPer = kCnt / kT;  // counters per thread: kPer / 2 whole pairs
-    // (the sink's records land past the copy-out; GL: a unit's run padded to 4)
-    constexpr uint32_t kRecWords = kTile * KM + (GL ? 4 * (kCnt / 2) : 0);
+    constexpr uint32_t kRecWords = kPTile * KM;  // (the sink's records land past the copy-out)
     constexpr uint32_t kCo = (kRecWords / 4 + kT - 1) / kT;  // 16-B copy-out pieces per thread
-    constexpr uint32_t kMap = GL ? kRecWords / 4 : 1;        // GL: a piece's place - its LDS place
     // the counter bias: counter c starts at c << kSB, so an atomic's return
     // value >> kRS (= kSB - 2) is its byte offset 4 c as long as 4 * rank
     // stays below bit kRS
     constexpr uint32_t kSB = 18, kRS = kSB - 2;
-    static_assert(kCnt % (2 * kT) == 0 && kRecWords < 65536u && kTile % kT == 0 && kTile <= 2048,
-                  "whole pairs per thread; starts fit 16 bits; 11-bit swipe field");
+    static_assert(kCnt % (2 * kT) == 0 && kRecWords < 65536u && kPTile % kT == 0 && kPTile <= 2048,
+                  "whole pairs per thread; starts fit 16 bits; a tile's swipes fit the 11-bit swipe field");
     static_assert(4u * kRecWords < (1u << kRS) && (2 * kCnt - 1) < (1u << (32 - kSB)),
                   "a rank * 4 below bit kRS; the bias of the last counter fits");
     // a counter's cleared value
@@ -364,7 +362,6 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
     struct __attribute__((aligned(16))) Lds {
         uint32_t cnt[2 * kCnt];
         uint32_t srec[kRecWords];
-        uint32_t dmap[kMap];
         uint32_t swsum[kT / 64];
         uint32_t stot;
     };
@@ -387,7 +384,7 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
     const __amdgpu_buffer_rsrc_t rhllw = part_rsrc(A.hllw, A.n * 4);
     const __amdgpu_buffer_rsrc_t roff = part_rsrc(A.off, nunits * A.off_stride * 4);
     auto offsets = [&](uint32_t t, uint32_t u, uint32_t &b, uint32_t &e) {
-        const uint32_t i = t * kTile + u * kT + tid;
+        const uint32_t i = t * kPTile + u * kT + tid;
         const uint32_t ic = i < A.n ? i : A.n - 1;
         // the swipe's two offsets in one 8-B load
         const uint2 lbe = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(roffs, ic * 4, 0, kNtAux<2>));
@@ -397,18 +394,13 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
     uint32_t gt0, gt1;
     part_group(A.ntiles, blockIdx.x % kPGroups, gt0, gt1);
     const uint32_t tstep = gridDim.x / kPGroups;
-    // this block's tiles: every tstep-th of its group's (GL: every tstep-th
-    // group of 8 tiles, its tiles in order; gt0 is a multiple of 8)
-    const uint32_t tfirst = GL ? gt0 + 8 * (blockIdx.x / kPGroups) : gt0 + blockIdx.x / kPGroups;
-    auto tnext = [&](uint32_t t) {
-        if constexpr (GL) return (t & 7u) != 7u && t + 1 < gt1 ? t + 1 : (t & ~7u) + 8 * tstep;
-        else return t + tstep;
-    };
+    // this block's tiles: every tstep-th of its group's
+    const uint32_t tfirst = gt0 + blockIdx.x / kPGroups;
+    auto tnext = [&](uint32_t t) { return t + tstep; };
     const __amdgpu_buffer_rsrc_t rbytes = part_rsrc(A.bytes, 0xfffffff0u);
     const PartLink &L = A.link[0];
     uint32_t nb_[kU], ne_[kU];
     PartId it[kU];
-    uint32_t gofs[kPer / 2] = {};  // GL: this thread's units' places in the current group
     {
         // the first tile's ids, then the second tile's offsets (a tile's ids
         // load at the start of the tile before it, from offsets loaded one
@@ -447,11 +439,11 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
         for (uint32_t u = 0; u < kU; u++) part_id_load(rbytes, nb_[u], ne_[u], itn[u]);
 #pragma unroll
         for (uint32_t u = 0; u < kU; u++) offsets(tn2, u, nb_[u], ne_[u]);
-        const bool full = (t + 1) * kTile <= A.n;  // block-uniform
+        const bool full = (t + 1) * kPTile <= A.n;  // block-uniform
 #pragma unroll
         for (uint32_t u = 0; u < kU; u++) {
             const uint32_t lu = u * kT + tid;
-            const uint32_t i = t * kTile + lu;
+            const uint32_t i = t * kPTile + lu;
             const bool act = i < A.n;
             uint64_t ha, hb, hh;
             part_hash3(A.bytes, it[u], ha, hb, hh);
@@ -498,7 +490,7 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
             v[j] = (cnt[c] - (c << kSB)) >> 2;
         }
 #pragma unroll
-        for (uint32_t j = 0; j < kPer; j += 2) s += GL ? (v[j] + v[j + 1] + 3) & ~3u : v[j] + v[j + 1];
+        for (uint32_t j = 0; j < kPer; j += 2) s += v[j] + v[j + 1];
         const uint32_t incl = part_wave_scan(s);
         if (lane == 63) swsum[wave] = incl;
         lds_barrier();  // 2
@@ -507,25 +499,13 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
 #pragma unroll
         for (uint32_t j = 0; j < kPer; j += 2) {
             const uint32_t g = tid * kPer + j, c = cb + g, un = g / 2, n2 = v[j] + v[j + 1];
-            uint32_t W = run | (n2 << 16);  // pass B's run: start | count << 16
-            if constexpr (GL) {
-                // the unit's next place in the group's region, or (it does not
-                // fit) its LDS place in the tile's overflow row: bit 31
-                const uint32_t p4 = (n2 + 3) & ~3u;
-                if ((t & 7u) == 0) gofs[j / 2] = 0;
-                const bool fits = gofs[j / 2] + p4 <= A.gcap;
-                const uint32_t dst = fits ? ((t >> 3) * nunits + un) * A.gcap + gofs[j / 2] : A.govf + t * A.stride + run;
-                W = fits ? gofs[j / 2] | (n2 << 16) : W | 0x80000000u;
-                if (fits) gofs[j / 2] += p4;
-                if (un < nunits)
-                    for (uint32_t p = run / 4; p < (run + p4) / 4; p++) lds.dmap[p] = dst - run;
-            }
-            __builtin_amdgcn_raw_buffer_store_b32(W, roff, un < nunits ? (un * A.off_stride + t) * 4 : kOOR, 0, 0);
+            // pass B's run: start | count << 16
+            __builtin_amdgcn_raw_buffer_store_b32(run | (n2 << 16), roff, un < nunits ? (un * A.off_stride + t) * 4 : kOOR, 0, 0);
             if (g == sink) stot = run;
             // (the slice's start in bytes: where its first record goes)
             cnt[c] = 4 * run - czero(c);
             cnt[c + 1] = 4 * (run + v[j]) - czero(c + 1);
-            run += GL ? (n2 + 3) & ~3u : n2;
+            run += n2;
         }
         lds_barrier();  // 3
 #pragma unroll
@@ -543,8 +523,7 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
         const uint32_t total = stot;
         // a fixed number of 16-B pieces per thread (those past the tile's
         // total go out of range)
-        const __amdgpu_buffer_rsrc_t rdst =
-            GL ? part_rsrc(A.rec, (A.govf + A.ntiles * A.stride) * 4) : part_rsrc(A.rec + size_t(t) * A.stride, A.stride * 4);
+        const __amdgpu_buffer_rsrc_t rdst = part_rsrc(A.rec + size_t(t) * A.stride, A.stride * 4);
         // (a piece past the records reads the last piece instead: an LDS read
         // past srec would be undefined behaviour, from which the compiler may
         // infer a bound on tid for the rest of the kernel -- round 4 had one:
@@ -566,7 +545,7 @@ __global__ void __launch_bounds__(512, 4) k_part_a3(const PartArgs A) {  // two 
         for (uint32_t c = 0; c < kCo; c++) {
             const uint32_t j = c * kT + tid;
             const uint32_t jr = (c + 1) * kT <= kLast + 1 ? j : (j < kLast ? j : kLast);
-            const uint32_t at = GL ? (j * 4 + lds.dmap[jr]) * 4 : j * 16;
+            const uint32_t at = j * 16;
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned int, src[jr]),
                                                    rdst, j * 4 < total ? at : kOOR, 0, kNtAux<4>);
         }
@@ -652,14 +631,10 @@ hipError_t set_pb_stamp_buffer(void *p) {
 // 8-tile group) space in equal contiguous shares, so no block runs a fifth
 // unit while the others wait (round 5: pass B 0.368 -> 0.362 ms per 2^25
 // sub-batch, three alternations; profiles/r05_ab_pass_b_split.txt)
-// GL (FL only): the group layout -- a run's start is its place in the (tile
-// group, unit) region, or (bit 31 of its run word) in the tile's overflow row
-// (a k_part_a3 record's swipe field is its bits 20..30)
-template <int SP, int R = 2 * SP, bool FL = false, bool GL = false>  // R: 16-byte pieces per lane and run (runs of SP slices)
+template <int SP, int R = 2 * SP, bool FL = false>  // R: 16-byte pieces per lane and run (runs of SP slices)
 __global__ void __launch_bounds__(kPbBlock, SP == 1 ? 8 : 4) k_part_b(const PartArgs A) {
-    static_assert(!GL || FL, "the group layout is pass A3's");
     PB_STAMP(0);
-    const uint32_t tmask = (1u << kPTileLog) - 1;
+    const uint32_t tmask = kPTile - 1;
     __shared__ __attribute__((aligned(16))) uint8_t img[kPSliceBytes * SP];
     __shared__ uint32_t fq[kPbBlock / 64][kPbQueue];
     // this block's share of the (slice unit, tile) space: XCD x (blocks b % 8
@@ -681,10 +656,9 @@ __global__ void __launch_bounds__(kPbBlock, SP == 1 ? 8 : 4) k_part_b(const Part
     // n * bi1 / nblk64) in 64-bit products.  The operands are named here,
     // ahead of take_rest, on purpose: the compiler then forms them in the
     // entry block, as it did up to round 7 (a share initialiser of the removed
-    // forms stood here), and three of this kernel's four instantiations keep
-    // that instruction stream exactly (the group layout's differs by one pair
-    // of loads, profiles/r08_refactor_ab.txt).  Folding them into take_rest
-    // changes the scalar prologue; re-measure pass B if you do.
+    // forms stood here), and every instantiation keeps that instruction
+    // stream exactly (profiles/r08_refactor_ab.txt).  Folding them into
+    // take_rest changes the scalar prologue; re-measure pass B if you do.
     const uint64_t bi0 = bi, nblk64 = nblk, bi1 = bi + 1;
     uint32_t w, wend;  // this block's current share of the space
     uint32_t su = bi;  // this block's current unit
@@ -710,12 +684,10 @@ __global__ void __launch_bounds__(kPbBlock, SP == 1 ? 8 : 4) k_part_b(const Part
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t k = lane / kPbLanes, qq = lane % kPbLanes;
     constexpr uint32_t kWaves = kPbBlock / 64, kStep = kWaves * kPbGroup;
-    // the records of this block's tile group (per-tile layout; offsets from
-    // its first tile, so a 2^26-swipe sub-batch's 2.95 GB stay 32-bit), or
-    // of every group (the group layout: regions and overflow rows)
-    const size_t rbase = GL ? 0 : size_t(gt0) * A.stride;
-    const __amdgpu_buffer_rsrc_t rrec =
-        GL ? part_rsrc(A.rec, (A.govf + A.ntiles * A.stride) * 4) : part_rsrc(A.rec + rbase, (gt1 - gt0) * A.stride * 4);
+    // the records of this block's tile group (offsets from its first tile,
+    // so a 2^26-swipe sub-batch's 2.95 GB stay 32-bit)
+    const size_t rbase = size_t(gt0) * A.stride;
+    const __amdgpu_buffer_rsrc_t rrec = part_rsrc(A.rec + rbase, (gt1 - gt0) * A.stride * 4);
     const __amdgpu_buffer_rsrc_t roff = part_rsrc(A.off, (A.nslices + 1) * A.off_stride * 4);
     const __amdgpu_buffer_rsrc_t rfl = part_rsrc(A.flist, FL ? A.nunits * A.fl_stride * kPbLanes * 2 : 0);
     uint32_t *q = fq[wave];
@@ -775,11 +747,7 @@ __global__ void __launch_bounds__(kPbBlock, SP == 1 ? 8 : 4) k_part_b(const Part
         auto load_be8 = [&](uint32_t tg0, uint32_t &B, uint32_t &E) {
             const uint32_t t = tg0 + (lane / kPbGroup) * kStep + lane % kPbGroup;
             const bool in = t < tb;
-            if constexpr (GL) {  // B keeps the overflow bit 31
-                const uint32_t W = __builtin_amdgcn_raw_buffer_load_b32(roff, in ? (orow + t) * 4 : kOOR, 0, kNtAux<1>);
-                B = W & 0x8000ffffu;
-                E = (W & 0xffffu) + ((W >> 16) & 0x7fffu);
-            } else if constexpr (FL) {
+            if constexpr (FL) {
                 const uint32_t W = __builtin_amdgcn_raw_buffer_load_b32(roff, in ? (orow + t) * 4 : kOOR, 0, kNtAux<1>);
                 B = W & 0xffffu;
                 E = B + (W >> 16);
@@ -792,15 +760,11 @@ __global__ void __launch_bounds__(kPbBlock, SP == 1 ? 8 : 4) k_part_b(const Part
         // its start: every piece is one whole line (one request, not two)
         // (one byte offset per lane; piece c adds 128 c, an immediate of the
         // load; a piece past the run's end goes out of range)
-        // the word where tile t's run of this unit is placed from (GL: its
-        // group region, or with bit 31 of b its overflow row)
-        auto row = [&](uint32_t t, uint32_t b) {
-            if constexpr (GL) return (b >> 31) ? A.govf + t * A.stride : ((t >> 3) * A.nunits + unit) * A.gcap;
-            else return (t - gt0) * A.stride;
-        };
+        // the word where tile t's run of this unit is placed from
+        auto row = [&](uint32_t t) { return (t - gt0) * A.stride; };
         auto load_recs = [&](uint32_t tg, uint32_t b, uint32_t e, uint4 (&r)[R]) {
-            const uint32_t i0 = (b & (GL ? 0xffe0u : ~31u)) + qq * 4;
-            const uint32_t v0 = (row(tg + k, b) + i0) * 4;
+            const uint32_t i0 = (b & ~31u) + qq * 4;
+            const uint32_t v0 = (row(tg + k) + i0) * 4;
             const int32_t left = int32_t(e) - int32_t(i0);
 #pragma unroll
             for (uint32_t c = 0; c < R; c++)
@@ -827,8 +791,7 @@ __global__ void __launch_bounds__(kPbBlock, SP == 1 ? 8 : 4) k_part_b(const Part
             load_recs(tg + kStep, b1, e1, rn);
             // the (up to) 4R records of this lane: piece c starts at record
             // lo_c = s0 + c*32 + qq*4; bit j of vm: record j in [bc, ec)
-            const uint32_t bw = GL ? bc & 0xffffu : bc;  // (GL: without the overflow bit)
-            const uint32_t s0 = bw & ~31u;
+            const uint32_t s0 = bc & ~31u;
             uint32_t rec[4 * R];
 #pragma unroll
             for (uint32_t c = 0; c < R; c++) {
@@ -847,7 +810,7 @@ __global__ void __launch_bounds__(kPbBlock, SP == 1 ? 8 : 4) k_part_b(const Part
             uint32_t vm = 0;
 #pragma unroll
             for (uint32_t c = 0; c < R; c++) vm |= part_bfm(clamp4(dh - int32_t(32 * c)), 4 * c);
-            vm &= ~part_bfm(clamp4(int32_t(bw) - int32_t(lo0)), 0);
+            vm &= ~part_bfm(clamp4(int32_t(bc) - int32_t(lo0)), 0);
             // bit set in the image: its 32-bit word, bit (offset & 31); with
             // slice pairs the record's parity bit selects the image half
             const uint32_t *img32 = reinterpret_cast<const uint32_t *>(img);
@@ -937,7 +900,7 @@ __global__ void __launch_bounds__(kPbBlock, SP == 1 ? 8 : 4) k_part_b(const Part
                 __builtin_amdgcn_wave_barrier();
             }
             if (ec - s0 > 32 * R) {  // rare: a long run
-                const uint32_t base = row(tg + k, bc);
+                const uint32_t base = row(tg + k);
                 for (uint32_t i = s0 + 32 * R + qq; i < ec; i += kPbLanes) {
                     const uint32_t rr = __builtin_amdgcn_raw_buffer_load_b32(rrec, (base + i) * 4, 0, 0);
                     const uint32_t o = FL ? (rr & 0xfffffu)
@@ -972,7 +935,7 @@ __global__ void __launch_bounds__(kPcBlock) k_part_c(const PartArgs A) {
     const uint32_t T = kPcBlock, tid = threadIdx.x;
     uint32_t gt0, gt1;
     part_group(A.ntiles, blockIdx.x % kPGroups, gt0, gt1);
-    const uint64_t tile = uint64_t(1) << kPTileLog;
+    const uint64_t tile = kPTile;
     const uint64_t end = uint64_t(gt1) * tile < A.n ? uint64_t(gt1) * tile : A.n;
     const uint64_t stride = uint64_t(gridDim.x / kPGroups) * T * U;
     for (uint64_t base = uint64_t(gt0) * tile + uint64_t(blockIdx.x / kPGroups) * T * U; base < end;
@@ -1037,7 +1000,7 @@ __global__ void __launch_bounds__(kPcBlock) k_part_c(const PartArgs A) {
 // (1024 x 1 since round 4; see kPcFlT).
 template <uint32_t BT, int U>
 __global__ void __launch_bounds__(BT) k_part_c_fl(const PartArgs A) {
-    constexpr uint32_t TILE = kTileFl;
+    constexpr uint32_t TILE = kPTile;
     static_assert(BT * U == TILE, "one tile per sub-step");
     constexpr uint32_t kPcFlBlock = BT;
     constexpr uint32_t kRun = kPbGroup;  // tiles per block iteration
@@ -1164,8 +1127,6 @@ static uint32_t part_km(uint32_t ksum) {
 // records per tile, rounded so tiles start on 128-B lines
 static uint32_t part_stride(uint32_t ksum, uint32_t tile) { return ((ksum * tile) + 31) & ~31u; }
 
-static_assert(kTileFl == kPaBlock, "every chain's tiles are 1024 swipes");
-
 static bool part_plan(const ChainDev &ch, PartArgs *A) {
     if (ch.nlinks < 1 || ch.nlinks > kPMaxLinks) return false;
     uint32_t slices = 0, ksum = 0;
@@ -1189,7 +1150,7 @@ static bool part_plan(const ChainDev &ch, PartArgs *A) {
     A->nslices = slices;
     A->ksum = ksum;
     A->nunits = (slices + 1) / 2;
-    A->stride = part_stride(ksum, kTileFl);
+    A->stride = part_stride(ksum, kPTile);
     return true;
 }
 
@@ -1198,42 +1159,17 @@ bool part_supported(const ChainDev &ch) {
     return part_plan(ch, &A);
 }
 
-// The group layout's geometry (k_part_a3<11, 1024, true>): a (group of 8
-// tiles, unit) region holds the unit's expected records of the group plus
-// six standard deviations, the runs' padding and a line; the overflow rows
-// after the regions take k_part_a3's padded LDS layout (stride 13 312).
-// False when the layout does not apply or its offsets would pass 2^31 bytes.
-// Only on request (rec_groups 1): at C3 it moves pass B 0.195 -> 0.183 ms
-// and pass A 0.226 -> 0.388 ms per 16 M sub-batch -- a run's edge lines are
-// written by two tiles, partial-line writes.
-static bool part_glayout(PartArgs *A, const SegOpts &so, uint32_t ntiles_max) {
-    A->gcap = A->govf = 0;
-    if (so.rec_groups != 1 || !part_flist(*A) || A->nunits >= 512) return false;
-    const double d = double(A->link[0].d);
-    const double share = std::min(d, double(2 * kPSliceBits)) / d;  // of the largest unit
-    const double mu = 8.0 * 1024 * A->ksum * share;
-    const uint64_t cap = (uint64_t(mu + 6 * std::sqrt(mu) + 8 * 3 + 32) + 31) & ~uint64_t(31);
-    const uint64_t stride = ((1024u * 11 + 4 * (1024 / 2)) + 31) & ~31u;
-    const uint64_t govf = uint64_t((ntiles_max + 7) / 8) * A->nunits * cap;
-    if (cap >= 65536 || (govf + uint64_t(ntiles_max) * stride) * 4 >= (uint64_t(1) << 31)) return false;
-    A->gcap = uint32_t(cap);
-    A->govf = uint32_t(govf);
-    A->stride = uint32_t(stride);
-    return true;
-}
-
 // the scratch of a sub-batch of up to `sub` swipes (context scratch slots
 // kScrPart*: probe records, run boundaries, fail bytes, HLL words, and the
 // fail lists of one-link chains)
-static hipError_t part_scratch(PartArgs *A, uint64_t n, uint32_t sub, const SegOpts &so, Scratch *scr) {
+static hipError_t part_scratch(PartArgs *A, uint64_t n, uint32_t sub, Scratch *scr) {
     const uint32_t m = n < sub ? uint32_t(n) : sub;
-    const uint32_t tile = kTileFl;
+    const uint32_t tile = kPTile;
     const uint32_t ntiles_max = (m + tile - 1) / tile;
     const uint32_t fstride = (m + 255) & ~255u;
     A->off_stride = (ntiles_max + 15) & ~15u;
     hipError_t e = hipSuccess;
-    part_glayout(A, so, ntiles_max);
-    A->rec = (uint32_t *)scratch_get(scr, kScrPartRec, (size_t(A->govf) + size_t(ntiles_max) * A->stride) * 4, &e);
+    A->rec = (uint32_t *)scratch_get(scr, kScrPartRec, size_t(ntiles_max) * A->stride * 4, &e);
     if (e == hipSuccess) A->off = (uint32_t *)scratch_get(scr, kScrPartOff, size_t(A->off_stride) * (A->nslices + 1) * 4, &e);
     // (fail bytes: the fail-list chains keep their overflow flags in the HLL words)
     A->fail = nullptr;
@@ -1256,7 +1192,7 @@ constexpr uint32_t kPSubDefault = 1u << 25;
 static uint32_t part_sub(uint32_t sub_opt, const PartArgs &A) {
     const uint64_t tiles = ((uint64_t(1) << 31) - 1) / (uint64_t(A.stride) * 4);
     const uint64_t span = (tiles - 8) * kPGroups;  // tiles a sub-batch may have
-    const uint32_t tile = kTileFl;
+    const uint32_t tile = kPTile;
     const uint32_t cap = uint32_t(std::min<uint64_t>(kPSub / tile * tile, span / 8 * 8 * tile));
     uint32_t sub = sub_opt ? sub_opt : std::min(cap, kPSubDefault);
     sub = (sub + tile - 1) / tile * tile;
@@ -1269,7 +1205,7 @@ hipError_t part_reserve(const ChainDev &ch, uint64_t n, uint32_t sub_opt, uint32
     PartArgs A{};
     if (!part_plan(ch, &A)) return hipErrorInvalidValue;
     const uint32_t sub = part_sub(sub_opt, A);
-    hipError_t e = part_scratch(&A, n ? n : 1, sub, so, scr);
+    hipError_t e = part_scratch(&A, n ? n : 1, sub, scr);
     SegPlan P;
     if (e == hipSuccess && seg_use(A, so, nslots, n ? n : 1, sub, &P)) {
         SegArgs S{};
@@ -1292,9 +1228,9 @@ hipError_t launch_swipes_part(const ChainDev &ch, const PartBatch *bt, uint32_t 
     uint64_t nmax = 0;
     for (uint32_t j = 0; j < nb; j++) nmax = bt[j].n > nmax ? bt[j].n : nmax;
     if (nmax == 0) return hipSuccess;
-    hipError_t e = part_scratch(&A, nmax, sub, so, scr);
+    hipError_t e = part_scratch(&A, nmax, sub, scr);
     if (e != hipSuccess) return e;
-    const uint32_t tile = kTileFl;
+    const uint32_t tile = kPTile;
     A.regs = regs;
     A.nslots = nslots;
     A.err = err;
@@ -1344,9 +1280,7 @@ hipError_t launch_swipes_part(const ChainDev &ch, const PartBatch *bt, uint32_t 
             A.slot = B.slot + s0;
             A.out = B.out ? B.out + s0 : nullptr;
             if (hook) hook(hook_user, 0, 0, st);
-            if (A.gcap)  // the group layout (C3/C5 by default)
-                hipLaunchKernelGGL((k_part_a3<11, 1024, true>), dim3(ga3), dim3(512), 0, st, A);
-            else if (flist && A.nunits < 512)  // C3/C5: 152 pairs, two counters per thread
+            if (flist && A.nunits < 512)  // C3/C5: 152 pairs, two counters per thread
                 hipLaunchKernelGGL((k_part_a3<11, 1024>), dim3(ga3), dim3(512), 0, st, A);
             else if (flist)
                 hipLaunchKernelGGL((k_part_a3<11, 2048>), dim3(ga3), dim3(512), 0, st, A);
@@ -1356,9 +1290,7 @@ hipError_t launch_swipes_part(const ChainDev &ch, const PartBatch *bt, uint32_t 
                 hipLaunchKernelGGL(k_part_a<22>, dim3(ga), dim3(kPaBlock), 0, st, A);
             if (hook) hook(hook_user, 0, 1, st);
             if (hook) hook(hook_user, 1, 0, st);
-            if (A.gcap)
-                hipLaunchKernelGGL((k_part_b<2, 4, true, true>), dim3(gb), dim3(kPbBlock), 0, st, A);
-            else if (flist)
+            if (flist)
                 // (4 pieces per lane: a (pair, tile) run of ~74 records from the
                 // line holding its start)
                 hipLaunchKernelGGL((k_part_b<2, 4, true>), dim3(gb), dim3(kPbBlock), 0, st, A);
@@ -1381,9 +1313,9 @@ hipError_t launch_swipes_part(const ChainDev &ch, const PartBatch *bt, uint32_t 
             if (hook) hook(hook_user, 2, 0, st);
             if (flist) {
                 const unsigned gc =
-                    (part_grid(ms, kTileFl * kPbGroup, unsigned(cus) * kPcFlBlocksPerCu) + kPGroups - 1) /
+                    (part_grid(ms, kPTile * kPbGroup, unsigned(cus) * kPcFlBlocksPerCu) + kPGroups - 1) /
                     kPGroups * kPGroups;
-                hipLaunchKernelGGL((k_part_c_fl<kPcFlT, kTileFl / kPcFlT>), dim3(gc), dim3(kPcFlT), 0, st, A);
+                hipLaunchKernelGGL((k_part_c_fl<kPcFlT, kPTile / kPcFlT>), dim3(gc), dim3(kPcFlT), 0, st, A);
             } else {
                 const unsigned gc = (part_grid(ms, kPcBlock * 2, unsigned(cus) * 8) + kPGroups - 1) / kPGroups * kPGroups;
                 hipLaunchKernelGGL(k_part_c<2>, dim3(gc), dim3(kPcBlock), 0, st, A);

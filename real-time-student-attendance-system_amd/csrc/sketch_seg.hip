@@ -140,11 +140,11 @@ __device__ __forceinline__ uint32_t seg_arena_slots(const SegArgs &S, unsigned i
 constexpr uint32_t kSegC1T = 512;
 template <uint32_t T> struct SegC1 {
     static constexpr uint32_t U = kSegRunSw / T;  // swipes per thread per run
-    static constexpr uint32_t PT = kTileFl / T;   // swipes per thread per tile
+    static constexpr uint32_t PT = kPTile / T;   // swipes per thread per tile
     static constexpr uint32_t BPC = 3;            // blocks per CU
     static constexpr uint32_t WPE = BPC * (T / 64) / 4;
     static_assert(T == 512, "three blocks per CU");
-    static_assert(kTileFl % T == 0, "whole tile slices per thread");
+    static_assert(kPTile % T == 0, "whole tile slices per thread");
 };
 template <uint32_t T>
 __global__ void __launch_bounds__(T, SegC1<T>::WPE) k_seg_c1(const PartArgs A, const SegArgs S) {
@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(T, SegC1<T>::WPE) k_seg_c1(const PartArgs A, c
         uint32_t sl[U], hv[U];
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) {  // swipe u: tile u / PT, its (u % PT)-th T-thread slice
-            const uint32_t i = (t0 + u / PT) * kTileFl + (u % PT) * T + tid;
+            const uint32_t i = (t0 + u / PT) * kPTile + (u % PT) * T + tid;
             const bool act = t0 + u / PT < t1 && i < A.n;
             sl[u] = act ? nt_ld<16>(A.slot + i) : 0u;
             hv[u] = act ? nt_ld<16>(A.hllw + i) : 0xff000000u;
@@ -189,12 +189,12 @@ __global__ void __launch_bounds__(T, SegC1<T>::WPE) k_seg_c1(const PartArgs A, c
             }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const uint32_t base = ((p0 + uint32_t(j) * T + tid) % kSegRunTiles) * kTileFl;
+                const uint32_t base = ((p0 + uint32_t(j) * T + tid) % kSegRunTiles) * kPTile;
 #pragma unroll
                 for (int c = 0; c < 4; c++) {
                     const uint32_t lo = e[j][c] & 0xffffu, hi = e[j][c] >> 16;
-                    if (ok[j] && lo < kTileFl) mark[base + lo] = ep;  // (0xffff: no entry)
-                    if (ok[j] && hi < kTileFl) mark[base + hi] = ep;
+                    if (ok[j] && lo < kPTile) mark[base + lo] = ep;  // (0xffff: no entry)
+                    if (ok[j] && hi < kPTile) mark[base + hi] = ep;
                 }
             }
         }
@@ -202,8 +202,8 @@ __global__ void __launch_bounds__(T, SegC1<T>::WPE) k_seg_c1(const PartArgs A, c
         uint32_t rec[U], pos[U];
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) {
-            const uint32_t lt = (u / PT) * kTileFl + (u % PT) * T + tid;  // the swipe's place in the run
-            const uint32_t i = t0 * kTileFl + lt;
+            const uint32_t lt = (u / PT) * kPTile + (u % PT) * T + tid;  // the swipe's place in the run
+            const uint32_t i = t0 * kPTile + lt;
             const bool act = t0 + u / PT < t1 && i < A.n;
             const bool valid = act && (hv[u] >> 24) == 0 && mark[lt] != ep;
             if (A.out && act) nt_st<16>(A.out + i, uint8_t(valid));

@@ -851,7 +851,8 @@ def test_product_options_only(engine):
     from rtsas_amd._lib import SKE_EINVAL
     lib, ptr = engine.ctx.lib, engine.ctx.ptr
     for name in [b"ablate", b"hll_mode", b"part_overlap", b"part_ccus", b"pa_tile", b"pa_precheck",
-                 b"pa_grid", b"pa_threads", b"pb_pairs", b"k1_legacy", b"xr_region_u", b"xr_finish_u"]:
+                 b"pa_grid", b"pa_threads", b"pb_pairs", b"k1_legacy", b"xr_region_u", b"xr_finish_u",
+                 b"rec_groups"]:
         assert lib.ske_set_option(ptr, name, 1) == SKE_EINVAL, name
     for name, val in [(b"variant", -1), (b"tile", 2), (b"k1_grid", 0), (b"k1_persistent", 1),
                       (b"part_sub", 0), (b"pass_timing", 0)]:

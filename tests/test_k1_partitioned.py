@@ -3,6 +3,9 @@ error channel of the enqueue-only calls, and graph / scratch safety.
 
 - multi-link chains through the partitioned kernel (links of different k,
   slices numbered across links), ragged ids of 0..40 bytes;
+- ragged batches in sub-batches of 29 tiles (empty and ragged XCD tile
+  groups), and batches where one id is repeated up to every swipe (every run
+  of a few units 1024 records long, all other units empty);
 - ske_swipes_many_async with an out-of-range HLL slot, enqueued directly and
   recorded into a graph: the sticky device error word surfaces as SKE_ERANGE
   at ske_check_errors / ske_sync (the swipe's BF.EXISTS answer is still
@@ -101,17 +104,24 @@ def test_c3_geometry_ragged_long_ids(engine, orc):
     assert valid.sum() > 80000
 
 
-def _c3_small(engine, n_members=200_000):
+def _c3_small(engine, n_members=200_000, n_keys=64, seed=None, **over):
     from rtsas_amd import synthetic
     w = synthetic.WORKLOADS["c3"]
-    w = synthetic.Workload(**{**w.__dict__, "n_members": n_members, "n_keys": 64,
-                              "zipf_lectures": 0, "zipf_days": 0})
-    engine.reserve(0, w.bf_error, w.bf_capacity)   # the 19.8 MB C3 geometry
-    p = engine.gen_params(w)
+    w = synthetic.Workload(**{**w.__dict__, "n_members": n_members, "n_keys": n_keys,
+                              "zipf_lectures": 0, "zipf_days": 0, **over})
+    engine.reserve(0, w.bf_error, w.bf_capacity)   # the 19.8 MB C3 geometry: 152 slice pairs
+    p = engine.gen_params(w) if seed is None else engine.gen_params(w, seed=seed)
     engine.preload(0, p, w.n_members)
     engine.hll_reserve(w.n_keys)
     assert engine.variant(0) == 3
     return w, p
+
+
+def _oracle_chain(engine, orc, w, p):
+    chain = orc.Chain(w.bf_capacity, w.bf_error)
+    mb = engine.members_batch(p, 0, w.n_members).to_host()
+    chain.madd_packed(mb[0], mb[1])
+    return chain
 
 
 @pytest.mark.parametrize("mode", ["direct", "graph"])
@@ -304,6 +314,64 @@ def test_partitioned_hot_register_and_many_keys(engine, orc):
     want, _, _ = orc.process_swipes(chain, regs, slot, buf2, offs)
     assert np.array_equal(out.to_host(np.uint8, b.n), want)
     assert np.array_equal(engine.registers_all(40_001), regs)
+
+
+@pytest.mark.parametrize("sub", [0, 29 * 1024])
+def test_ragged_batches_and_29_tile_sub_batches_vs_oracle(engine, orc, sub):
+    """Ragged batches (1 swipe, a partial tile, a partial last group of 8
+    tiles) whole and in sub-batches of 29 tiles -- not a multiple of 8, so
+    some of the 8 XCD tile groups are empty and others ragged -- == the
+    oracle, answers and registers over the batches in order."""
+    from rtsas_amd.engine import DeviceBuffer
+    w, p = _c3_small(engine, 300_000, 97, seed=5151, invalid_frac=0.5)
+    engine.set_option("part_sub", sub)
+    chain = _oracle_chain(engine, orc, w, p)
+    regs = np.zeros((w.n_keys, 16384), np.uint8)
+    start = 0
+    for n in [1, 1000, 8 * 1024 * 3 + 777, 700_000 + 333]:
+        b = engine.swipe_batch(p, start, n)
+        start += n
+        out = DeviceBuffer(engine.ctx, b.n)
+        engine.swipes(0, b, out)
+        buf, offs, slot = b.to_host()
+        v, _, _ = orc.process_swipes(chain, regs, slot.astype(np.uint32), buf, offs)
+        assert np.array_equal(out.to_host(np.uint8, b.n), v)
+    assert np.array_equal(engine.registers_all(w.n_keys), regs)
+
+
+def _with_hot(engine, b, frac, rng):
+    """b with a fraction `frac` of its swipes replaced by its first id (one
+    key for them all)"""
+    from rtsas_amd.engine import DeviceBatch
+    buf, offs, slot = b.to_host()
+    assert np.all(np.diff(offs.astype(np.int64)) == 8)
+    ids = buf[:offs[-1]].reshape(-1, 8).copy()
+    hot = rng.random(b.n) < frac
+    ids[hot] = ids[0]
+    slot = slot.astype(np.uint32).copy()
+    slot[hot] = 3
+    buf2 = np.concatenate([ids.reshape(-1), np.zeros(16, np.uint8)])
+    return DeviceBatch.from_host(engine.ctx, buf2, offs, slot), (buf2, offs, slot)
+
+
+@pytest.mark.parametrize("frac", [0.05, 0.3, 1.0])
+def test_one_id_repeated_vs_oracle(engine, orc, frac):
+    """A fraction of the swipes repeat one id on one key, so the (at most 11)
+    units its probes land in get long runs.  At 1.0 every other unit is
+    empty, every run of those units is 1024 records and pass B's long-run
+    tail loop carries the whole batch; answers and registers == the oracle."""
+    from rtsas_amd.engine import DeviceBuffer
+    w, p = _c3_small(engine, 200_000, 64, seed=5151, invalid_frac=0.5)
+    rng = np.random.default_rng(int(frac * 1000) + 7)
+    b0 = engine.swipe_batch(p, 0, 600_000 + 123)
+    d, (buf, offs, slot) = _with_hot(engine, b0, frac, rng)
+    out = DeviceBuffer(engine.ctx, d.n)
+    engine.swipes(0, d, out)
+    chain = _oracle_chain(engine, orc, w, p)
+    regs = np.zeros((w.n_keys, 16384), np.uint8)
+    v, _, _ = orc.process_swipes(chain, regs, slot, buf, offs)
+    assert np.array_equal(out.to_host(np.uint8, d.n), v)
+    assert np.array_equal(engine.registers_all(w.n_keys), regs)
 
 
 @pytest.mark.parametrize("mode", ["direct", "graph"])
