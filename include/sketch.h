@@ -29,7 +29,8 @@
  *   - filters are addressed by a caller-chosen id `fid` < SKE_MAX_FILTERS, HLL
  *     keys by a caller-chosen register-slab slot, Count-Min Sketch tables by a
  *     caller-chosen `cid` < SKE_MAX_CMS, heavy-hitter sets by a caller-chosen
- *     `hid` < SKE_MAX_HH, time profiles by a caller-chosen `tid` < SKE_MAX_TP.
+ *     `hid` < SKE_MAX_HH, time profiles by a caller-chosen `tid` < SKE_MAX_TP,
+ *     tallies by a caller-chosen `tid` < SKE_MAX_TALLY (a space of their own).
  *     The facade maps Redis key names to fids / slots /
  *     cids.
  */
@@ -74,6 +75,11 @@ extern "C" {
 /* -28 is not assigned */
 #define SKE_ETPNOSET -29     /* time profile id not in use */
 #define SKE_ETPEXISTS -30    /* ske_tp_init on an id in use */
+/* -31 is not assigned */
+#define SKE_ETALLYNOSET -32  /* tally id not in use */
+#define SKE_ETALLYEXISTS -33 /* ske_tally_init on an id in use */
+#define SKE_ETALLYCAP -34    /* capacity_log2 outside [SKE_TALLY_MIN_LOG2, SKE_TALLY_MAX_LOG2] */
+#define SKE_ETALLYSPACE -35  /* ske_tally_list: more entries pass than the output arrays hold */
 
 #define SKE_MEM_HOST 0
 #define SKE_MEM_DEVICE 1
@@ -93,6 +99,13 @@ extern "C" {
 #define SKE_HH_MAX_RANKS 16  /* ranks one ske_hh_select carries */
 #define SKE_MAX_TP 256
 #define SKE_TP_BINS 168      /* weekday * 24 + hour, Monday = 0 */
+#define SKE_MAX_TALLY 256
+#define SKE_TALLY_KEY_BYTES 32 /* the longest key a tally groups */
+#define SKE_TALLY_MIN_LOG2 8
+#define SKE_TALLY_MAX_LOG2 24
+#define SKE_TALLY_MAX_PROBES 128 /* slots one insert-or-add looks at before it gives up */
+#define SKE_TALLY_LOAD_DEN 2   /* new keys are refused once used >= capacity / SKE_TALLY_LOAD_DEN */
+#define SKE_TALLY_MAX_TOP 16   /* entries per end one ske_tally_top returns */
 #define SKE_HLL_REGISTERS 16384
 #define SKE_HLL_DENSE_BYTES 12288
 #define SKE_HLL_DUMP_MAX_KEYS (1u << 18)   /* 2^18 * 12304 B < 2^32: u32 offsets suffice */
@@ -464,6 +477,100 @@ int ske_tp_import(ske_ctx *ctx, uint32_t tid, const uint64_t *in168);
 int ske_tp_add_async(ske_ctx *ctx, uint32_t tid, const int64_t *epoch, uint64_t n,
                      const uint8_t *mask_or_null, int want, uint32_t late_from, uint8_t *late_or_null);
 
+/* ---- tallies: exact event counts per key ----
+ * The group-by-count of a string column: every item of a batch adds 1 to its
+ * key's `events` and, when the batch has a mask and the item's mask byte is 1,
+ * 1 to its key's `valid` (invalid = events - valid; a caller without validity
+ * passes no mask and reads `events` alone).  A key is any byte string of at
+ * most SKE_TALLY_KEY_BYTES bytes; the empty string is a key and counts; the
+ * length takes part in identity (b"A" and b"A\0" are two keys).  A tally is an
+ * insert-only open-addressing table of 2^capacity_log2 device slots, addressed
+ * by a caller-chosen tid < SKE_MAX_TALLY; the context owns it.
+ *   replaces: df.groupby('lecture_id').size() of "Lecture Attendance Rankings"
+ *   (attendance_analysis.py:87-97, there pandas over Cassandra rows), and the
+ *   attendance_records count of attendance_processor.py:154-165.
+ * Results are integers and order-free inside and across batches: identical from
+ * run to run, apart from which of two digest-colliding keys names an entry.
+ *
+ * Limits: keys with the same 64-bit digest (MurmurHash64A of the key bytes, the
+ * Bloom seed; 0 mapped to 1) are one entry, the first to claim the slot names
+ * it.  An insert-or-add looks at SKE_TALLY_MAX_PROBES slots at most, and new
+ * keys are refused once capacity / SKE_TALLY_LOAD_DEN slots are used (a batch in
+ * flight may pass that mark by the claims racing at that moment, never the
+ * capacity).  A refused item is not grouped: its counts go to dropped_events /
+ * dropped_valid and the sticky overflow word is set, as for a key longer than
+ * SKE_TALLY_KEY_BYTES.  So always, complete or not,
+ *   sum of all events + dropped_events == taken,  the same for valid,
+ * where taken counts every item looked at.  While overflow is 0 every listed
+ * count is exact.  Once it is set listed counts are lower bounds, also those of
+ * keys the table holds: the load bound is read before the claim, so one thread
+ * can be refused a key at the moment another claims it.  Entries are never
+ * removed one by one; ske_tally_reset empties the tally. */
+typedef struct {
+    uint64_t capacity;        /* slots */
+    uint64_t used;            /* keys held */
+    uint64_t overflow;        /* non-zero once an item was refused */
+    uint64_t taken;           /* items looked at */
+    uint64_t dropped_events;  /* items not grouped */
+    uint64_t dropped_valid;   /* of those, the ones whose mask byte was 1 */
+} ske_tally_info_t;
+/* zeroed; SKE_ETALLYEXISTS when tid is in use, SKE_ETALLYCAP for a capacity out of range */
+int ske_tally_init(ske_ctx *ctx, uint32_t tid, uint32_t capacity_log2);
+/* SKE_EBUSY while a recorded graph is alive or being recorded */
+int ske_tally_free(ske_ctx *ctx, uint32_t tid);
+/* an empty, complete tally again (slots, counters and the head zeroed) */
+int ske_tally_reset(ske_ctx *ctx, uint32_t tid);
+int ske_tally_info(ske_ctx *ctx, uint32_t tid, ske_tally_info_t *out);
+/* One batch of keys on the device, enqueue only and graph-capturable; n < 2^32 - 1;
+ * mask NULL or one byte per item.  A key longer than SKE_TALLY_KEY_BYTES has no
+ * error path here: it is not grouped, counts as dropped and sets overflow.
+ *   packed: key i = bytes[offs[i] .. offs[i + 1]) (offs n + 1 entries; bytes
+ *     readable to the next 8-byte boundary behind the last key);
+ *   fixed: key i = the `width` bytes at keys + i * width (width 0: SKE_EINVAL);
+ *   spans: key i = bytes[start[i] .. start[i] + len[i]), taken only when status
+ *     is NULL or status[i] == 0 -- a column of ske_ingest_parse read in place
+ *     (lec_start / lec_len, masked by the BF.EXISTS bytes).  Only the aligned
+ *     8-byte words that hold a byte of the span are read, never past the 8-byte
+ *     boundary behind bytes. */
+int ske_tally_add_packed_async(ske_ctx *ctx, uint32_t tid, const uint8_t *bytes_dev, const uint32_t *offs_dev,
+                               uint64_t n, const uint8_t *mask_or_null);
+int ske_tally_add_fixed_async(ske_ctx *ctx, uint32_t tid, const uint8_t *keys_dev, uint32_t width, uint64_t n,
+                              const uint8_t *mask_or_null);
+int ske_tally_add_spans_async(ske_ctx *ctx, uint32_t tid, const uint8_t *bytes_dev, const uint32_t *start_dev,
+                              const uint32_t *len_dev, uint64_t n, const uint8_t *status_or_null,
+                              const uint8_t *mask_or_null);
+/* The packed form over host or device arrays (mem covers bytes, offs and mask);
+ * returns when done.  A key longer than SKE_TALLY_KEY_BYTES fails the call with
+ * SKE_ETOOLONG: with SKE_MEM_HOST before anything is counted, with
+ * SKE_MEM_DEVICE after the batch was (the long keys as dropped). */
+int ske_tally_add(ske_ctx *ctx, uint32_t tid, const uint8_t *bytes, const uint32_t *offs, uint64_t n,
+                  const uint8_t *mask_or_null, int mem);
+/* events_out[i], valid_out[i] = the counters of key i; 0, 0 for an absent (or too long) key */
+int ske_tally_query(ske_ctx *ctx, uint32_t tid, const uint8_t *bytes, const uint32_t *offs, uint64_t n,
+                    uint64_t *events_out, uint64_t *valid_out, int mem);
+/* Every entry with events >= min_events (0: all), sorted by events descending,
+ * then key bytes ascending, a shorter key first when it is a prefix of the other
+ * (host arrays: out_keys cap x SKE_TALLY_KEY_BYTES bytes, zero padded; the
+ * others cap entries).  *n_out = how many pass; more than cap: SKE_ETALLYSPACE
+ * and nothing is written (cap >= used always suffices).  *complete = 0 once an
+ * item was refused. */
+int ske_tally_list(ske_ctx *ctx, uint32_t tid, uint64_t min_events, uint8_t *out_keys, uint32_t *out_lens,
+                   uint64_t *out_events, uint64_t *out_valid, uint64_t cap, uint64_t *n_out, int *complete);
+/* The first k and the last k entries of that order, by events (by == 0) or with
+ * valid in the place of events (by == 1); 1 <= k <= SKE_TALLY_MAX_TOP, host
+ * arrays of k entries each.  *n_out = entries written to each end: min(k, keys
+ * held).  The tail comes in list order (its last entry is the listing's last),
+ * as .tail(k) prints it. */
+int ske_tally_top(ske_ctx *ctx, uint32_t tid, uint32_t k, int by, uint8_t *head_keys, uint32_t *head_lens,
+                  uint64_t *head_events, uint64_t *head_valid, uint8_t *tail_keys, uint32_t *tail_lens,
+                  uint64_t *tail_events, uint64_t *tail_valid, uint64_t *n_out, int *complete);
+/* Host arrays in the listing's layout: insert-or-ADD of n entries (a restore
+ * into an empty tally; the sum of several ranks' listings).  taken grows by the
+ * events.  A length over SKE_TALLY_KEY_BYTES: SKE_ETOOLONG; valid[i] >
+ * events[i] or non-zero padding: SKE_EINVAL; nothing is added then. */
+int ske_tally_import(ske_ctx *ctx, uint32_t tid, const uint8_t *keys, const uint32_t *lens, const uint64_t *events,
+                     const uint64_t *valid, uint64_t n);
+
 /* ---- the fused hot path (K1) ----
  * For every swipe i: v = BF.EXISTS fid id_i; if v: PFADD slot_i id_i.
  *   replaces the per-event pair attendance_processor.py:109-113 + :127-129.
@@ -669,6 +776,7 @@ int ske_ingest_dense(ske_ctx *ctx, const uint8_t *msgs, const ske_ingest_cols_t 
  * context stream (only enqueue-only calls: ske_swipes_async,
  * ske_swipes_fixed_async, ske_cms_add_fixed_async, ske_cms_add_packed_async,
  * ske_hh_track_fixed_async, ske_hh_track_packed_async, ske_tp_add_async,
+ * ske_tally_add_packed_async, ske_tally_add_fixed_async, ske_tally_add_spans_async,
  * ske_ingest_times) into an executable graph, uploaded to the device;
  * each ske_graph_launch replays it on the context stream.  A consumer that
  * processes a ring of fixed device batch slots replays one graph per turn of

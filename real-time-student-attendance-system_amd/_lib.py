@@ -45,6 +45,10 @@ SKE_EHHCAP = -26
 SKE_EHHSPACE = -27
 SKE_ETPNOSET = -29
 SKE_ETPEXISTS = -30
+SKE_ETALLYNOSET = -32
+SKE_ETALLYEXISTS = -33
+SKE_ETALLYCAP = -34
+SKE_ETALLYSPACE = -35
 SKE_MEM_HOST = 0
 SKE_MEM_DEVICE = 1
 SKE_MAX_FILTERS = 4096
@@ -59,6 +63,13 @@ SKE_HH_LOAD_DEN = 2
 SKE_HH_MAX_RANKS = 16
 SKE_MAX_TP = 256
 SKE_TP_BINS = 168
+SKE_MAX_TALLY = 256
+SKE_TALLY_KEY_BYTES = 32
+SKE_TALLY_MIN_LOG2 = 8
+SKE_TALLY_MAX_LOG2 = 24
+SKE_TALLY_MAX_PROBES = 128
+SKE_TALLY_LOAD_DEN = 2
+SKE_TALLY_MAX_TOP = 16
 HLL_REGISTERS = 16384
 HLL_DENSE_BYTES = 12288
 SKE_HLL_DUMP_MAX_KEYS = 1 << 18
@@ -98,6 +109,12 @@ class HhStats(C.Structure):
     _fields_ = [("n", C.c_uint64), ("sum", C.c_uint64), ("sq_lo", C.c_uint64), ("sq_hi", C.c_uint64),
                 ("min", C.c_uint32), ("max", C.c_uint32), ("med_lo", C.c_uint32), ("med_hi", C.c_uint32),
                 ("complete", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TallyInfo(C.Structure):
+    """ske_tally_info_t (include/sketch.h)."""
+    _fields_ = [("capacity", C.c_uint64), ("used", C.c_uint64), ("overflow", C.c_uint64), ("taken", C.c_uint64),
+                ("dropped_events", C.c_uint64), ("dropped_valid", C.c_uint64)]
 
 
 class IngestCols(C.Structure):
@@ -200,6 +217,20 @@ SIGNATURES = {
     "ske_tp_read": (C.c_int, [_CTX, C.c_uint32, _u64p]),
     "ske_tp_import": (C.c_int, [_CTX, C.c_uint32, _u64p]),
     "ske_tp_add_async": (C.c_int, [_CTX, C.c_uint32, _vp, C.c_uint64, _u8p, C.c_int, C.c_uint32, _u8p]),
+    "ske_tally_init": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),
+    "ske_tally_free": (C.c_int, [_CTX, C.c_uint32]),
+    "ske_tally_reset": (C.c_int, [_CTX, C.c_uint32]),
+    "ske_tally_info": (C.c_int, [_CTX, C.c_uint32, C.POINTER(TallyInfo)]),
+    "ske_tally_add_packed_async": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, C.c_uint64, _u8p]),
+    "ske_tally_add_fixed_async": (C.c_int, [_CTX, C.c_uint32, _u8p, C.c_uint32, C.c_uint64, _u8p]),
+    "ske_tally_add_spans_async": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, _u32p, C.c_uint64, _u8p, _u8p]),
+    "ske_tally_add": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, C.c_uint64, _u8p, C.c_int]),
+    "ske_tally_query": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, C.c_uint64, _u64p, _u64p, C.c_int]),
+    "ske_tally_list": (C.c_int, [_CTX, C.c_uint32, C.c_uint64, _u8p, _u32p, _u64p, _u64p, C.c_uint64,
+                                 C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "ske_tally_top": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_int, _u8p, _u32p, _u64p, _u64p, _u8p, _u32p,
+                                _u64p, _u64p, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "ske_tally_import": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, _u64p, _u64p, C.c_uint64]),
     "ske_swipes": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p, C.c_int]),
     "ske_swipes_async": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p]),
     "ske_swipes_fixed": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, C.c_uint32, C.c_uint64, _u8p,

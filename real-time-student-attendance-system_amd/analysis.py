@@ -40,7 +40,7 @@ import numpy as np
 from ._lib import IngestDense, SKE_MEM_DEVICE
 from .client_ingest import join_messages
 from .encoding import encode, pack
-from .engine import DeviceBuffer, hh_list
+from .engine import DeviceBuffer, hh_list, tally_query
 
 
 DAY_NAMES = ("Monday", "Tuesday", "Wednesday", "Thursday", "Friday", "Saturday", "Sunday")
@@ -125,13 +125,26 @@ class StudentCounts:
     heavy-hitter set.  ``day_profile``: the name of a time profile
     (``client.tp_create``; made here when it does not exist) that counts every
     swipe by weekday and hour.  With either set ``update`` needs the swipes'
-    times; with only ``late_key`` the profile is named ``b"tp:" + late_key``."""
+    times; with only ``late_key`` the profile is named ``b"tp:" + late_key``.
+
+    ``lecture_counts`` (default None: off): the name of a tally
+    (``client.tally_create``; made here with ``2 ** lecture_capacity_log2``
+    slots when it does not exist) that counts every swipe, valid or not, by
+    lecture -- the reference's ``groupby('lecture_id').size()``
+    (attendance_analysis.py:87-97) -- and the valid ones beside.  The group key
+    is the text ``keyspace.day_key`` puts into the key name,
+    ``str(lecture_id).encode()``, at most 32 bytes.  With it set ``update`` and
+    ``count_packed`` need the swipes' ``lectures``; ``update_messages`` reads
+    them from the messages."""
 
     def __init__(self, client, attended_key="cms:attended", invalid_key="cms:invalid",
                  error: float = 0.001, probability: float = 0.01, track_attended: int | None = None,
                  track_invalid: int | None = None, capacity_log2: int = 16, late_key=None,
-                 late_from: int = 9 * 3600, track_late: int | None = None, day_profile=None):
+                 late_from: int = 9 * 3600, track_late: int | None = None, day_profile=None,
+                 lecture_counts=None, lecture_capacity_log2: int = 16):
         self.client = client
+        self._lectures = encode(lecture_counts) if lecture_counts is not None else None
+        self._lec_bufs = None
         self.attended_key, self.invalid_key = attended_key, invalid_key
         self.late_key, self.late_from = late_key, int(late_from)
         if not 0 <= self.late_from <= 86400:
@@ -168,6 +181,8 @@ class StudentCounts:
             self._profile = encode(day_profile) if day_profile is not None else b"tp:" + encode(late_key)
             if self._profile not in client._tp:
                 client.tp_create(self._profile)
+        if self._lectures is not None and self._lectures not in client._tally:
+            client.tally_create(self._lectures, lecture_capacity_log2)
 
     def _buffers(self, n: int, width: int):
         b = self._bufs
@@ -184,7 +199,44 @@ class StudentCounts:
             self._bufs = b
         return b[2:]
 
-    def update(self, bf_key, slots: np.ndarray, ids: np.ndarray, times=None) -> np.ndarray:
+    def _check_lectures(self, lectures, n: int):
+        """The swipes' lectures as a packed batch ``(buf, offs)`` (None when
+        the option is off): a packed pair is taken as it is, a sequence is
+        encoded as ``keyspace.day_key`` names the lecture, ``str(x).encode()``."""
+        if (lectures is None) != (self._lectures is None):
+            raise ValueError("lectures go with lecture_counts: required with it, refused without")
+        if lectures is None:
+            return None
+        if isinstance(lectures, tuple) and len(lectures) == 2 and isinstance(lectures[1], np.ndarray):
+            buf = np.ascontiguousarray(lectures[0], dtype=np.uint8).reshape(-1)
+            offs = np.ascontiguousarray(lectures[1], dtype=np.uint32).reshape(-1)
+        else:
+            buf, offs = pack([x if isinstance(x, bytes) else str(x) for x in lectures])
+        if offs.size != n + 1:
+            raise ValueError("one lecture per id")
+        return buf, offs
+
+    def _enqueue_lectures(self, lec, n: int, d_valid) -> None:
+        """Upload the packed lectures and enqueue their tally add, masked by
+        the swipes' valid bytes (on the device already)."""
+        buf, offs = lec
+        nbytes = int(offs[-1])
+        b = self._lec_bufs
+        if b is None or b[0] < n or b[1] < nbytes:
+            if b is not None:
+                for x in b[2:]:
+                    x.free()
+            cn, cb = max(n, 1024), max(nbytes, 1 << 14)
+            ctx = self.client.ctx
+            b = (cn, cb, DeviceBuffer(ctx, cb + 64), DeviceBuffer(ctx, (cn + 1) * 4))
+            self._lec_bufs = b
+        b[2].from_host(buf[:nbytes])
+        b[3].from_host(offs)
+        cl = self.client
+        cl.ctx.call("ske_tally_add_packed_async", cl.tally_tid(self._lectures), C.c_void_p(b[2].ptr),
+                    C.c_void_p(b[3].ptr), n, C.c_void_p(d_valid.ptr))
+
+    def update(self, bf_key, slots: np.ndarray, ids: np.ndarray, times=None, lectures=None) -> np.ndarray:
         """One batch of swipes: ``client.swipes_fixed`` semantics (BF.EXISTS
         of every id, PFADD of the valid ones into their HLL slot), then every
         valid swipe's id counts in the attended key and every invalid one's
@@ -192,7 +244,10 @@ class StudentCounts:
         slot per swipe (``client.key_slot``).  ``times`` (one per swipe, any
         form ``epoch_seconds`` takes; required with ``late_key`` or
         ``day_profile``, refused without): every swipe counts in the profile,
-        every late one's id in the late key.  Returns the validity (bool)."""
+        every late one's id in the late key.  ``lectures`` (one per swipe, a
+        sequence or a packed ``(buf, offs)``; required with ``lecture_counts``,
+        refused without): every swipe counts under its lecture.  Returns the
+        validity (bool)."""
         cl = self.client
         ids = np.ascontiguousarray(ids, dtype=np.uint8)
         if ids.ndim != 2:
@@ -205,6 +260,7 @@ class StudentCounts:
             ep = epoch_seconds(times)
             if ep.size != n:
                 raise ValueError("one time per id")
+        lec = self._check_lectures(lectures, n)
         if n == 0 or width == 0:
             return np.zeros(n, bool)
         s = np.ascontiguousarray(slots, dtype=np.uint32)
@@ -241,6 +297,8 @@ class StudentCounts:
             hid, cid = cl._hh_entry(name)
             cl.ctx.call("ske_hh_track_fixed_async", hid, cid, C.c_void_p(d_ids.ptr), width, n,
                         C.c_void_p(d_time[1].ptr), want, thr)
+        if lec is not None:  # every swipe by its lecture, the valid ones beside
+            self._enqueue_lectures(lec, n, d_valid)
         cl.ctx.call("ske_sync")
         return d_valid.to_host(np.uint8, n).astype(bool)
 
@@ -249,6 +307,11 @@ class StudentCounts:
         """Whether the counting calls take the swipes' times (``late_key`` /
         ``day_profile``)."""
         return self._profile is not None
+
+    @property
+    def counts_lectures(self) -> bool:
+        """Whether the counting calls take the swipes' lectures (``lecture_counts``)."""
+        return self._lectures is not None
 
     def _enqueue_packed(self, d_ids, d_offs, n: int, d_valid, d_epoch, d_late) -> None:
         """The counting half of ``update`` over a packed batch on the device
@@ -308,13 +371,13 @@ class StudentCounts:
             raise ValueError("one time per id")
         return ep
 
-    def count_packed(self, buf, offs, valid, times=None) -> None:
+    def count_packed(self, buf, offs, valid, times=None, lectures=None) -> None:
         """The counting half of ``update`` for swipes whose BF.EXISTS answers
         the caller already has: id i is ``buf[offs[i]:offs[i + 1]]`` (the ids
         as redis-py encodes them, ``encoding.pack``), ``valid`` one answer per
         id.  Every valid swipe's id counts in the attended key and every
-        invalid one's in the invalid key; ``times`` as in ``update``.  No
-        swipe call is made.  Uploads, enqueues, returns when done."""
+        invalid one's in the invalid key; ``times`` and ``lectures`` as in
+        ``update``.  No swipe call is made.  Uploads, enqueues, returns when done."""
         buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
         offs = np.ascontiguousarray(offs, dtype=np.uint32).reshape(-1)
         n = offs.size - 1
@@ -322,6 +385,7 @@ class StudentCounts:
         if n < 0 or v.size != n:
             raise ValueError("one valid answer per id, offs one entry more")
         ep = self._check_times(times, n)
+        lec = self._check_lectures(lectures, n)
         if n == 0:
             return
         b = self._packed_buffers("host", n, int(offs[-1]))
@@ -332,6 +396,8 @@ class StudentCounts:
             b["epoch"].from_host(ep)
         self._enqueue_packed(b["ids"], b["offs"], n, b["valid"], b["epoch"] if ep is not None else None,
                              b.get("late"))
+        if lec is not None:
+            self._enqueue_lectures(lec, n, b["valid"])
         self.client.ctx.call("ske_sync")
 
     def update_messages(self, bf_key, messages, hll_key_prefix: str = "hll:unique:", key_form: str = "readme"):
@@ -343,8 +409,10 @@ class StudentCounts:
         decoded on the device are counted there: their ids, answers and times
         never come to the host.  The others are decoded by Python, as
         ``ingest`` does, and counted through ``count_packed``; a message that
-        cannot be decoded (status -1) counts nowhere.  Returns ``(valid,
-        status)`` as ``ingest``."""
+        cannot be decoded (status -1) counts nowhere.  With ``lecture_counts``
+        every counted message also counts under its ``lecture_id``: the
+        device-decoded ones from the lecture spans the parse left beside the
+        message bytes.  Returns ``(valid, status)`` as ``ingest``."""
         blob, moffs = join_messages(messages)
         return self.update_messages_packed(bf_key, blob, moffs, hll_key_prefix, key_form)
 
@@ -370,10 +438,15 @@ class StudentCounts:
         if ndense.value:
             self._enqueue_packed(d["ids"], d["offs"], int(ndense.value), d["valid"],
                                  d["epoch"] if self.timed else None, d["late"])
+            if self._lectures is not None:  # the lecture spans of the parse columns, in place
+                cl.ctx.call("ske_tally_add_spans_async", cl.tally_tid(self._lectures), msgs, run.cols.lec_start,
+                            run.cols.lec_len, n, run.cols.status,
+                            C.c_void_p(B["valid"].ptr) if run.has_bf else None)
             cl.ctx.call("ske_sync")
         if run.host_at:
             hbuf, hoffs = pack(run.host_ids)
-            self.count_packed(hbuf, hoffs, valid[np.asarray(run.host_at)], run.host_ts if self.timed else None)
+            self.count_packed(hbuf, hoffs, valid[np.asarray(run.host_at)], run.host_ts if self.timed else None,
+                              run.host_lectures if self._lectures is not None else None)
         return valid, status
 
     def _query(self, key, ids) -> np.ndarray:
@@ -472,6 +545,33 @@ class StudentCounts:
             raise ValueError("no late_key is tracked (track_late)")
         return self._top(self.late_key, k, threshold)
 
+    def lecture_events(self, lectures):
+        """``(events, valid)``, u64 per lecture: the swipes counted under it,
+        valid or not, and the valid ones; 0, 0 for a lecture never seen.
+        ``lectures`` as ``update`` takes them."""
+        if self._lectures is None:
+            raise ValueError("no lecture_counts")
+        lectures = list(lectures)
+        buf, offs = self._check_lectures(lectures, len(lectures))
+        return tally_query(self.client.ctx, self.client.tally_tid(self._lectures), buf, offs)
+
+    def lecture_rankings(self, k: int = 3, by: str = "events") -> dict:
+        """The reference's ``groupby('lecture_id').size().sort_values(
+        ascending=False)``, ``.head(k)`` and ``.tail(k)`` (attendance_analysis.py
+        :87-97): ``{"most_attended": {lecture: count}, "least_attended": {...},
+        "complete": bool}`` in the listing's total order (count descending,
+        lecture ascending; pandas leaves ties in quicksort order), the tail as
+        ``.tail(k)`` lists it.  ``by="valid"`` ranks and reports the valid
+        swipes instead.  ``complete`` False: the tally refused a swipe and the
+        counts are lower bounds."""
+        if self._lectures is None:
+            raise ValueError("no lecture_counts")
+        head, tail, complete = self.client.tally_top(self._lectures, k, by)
+        col = 2 if by == "valid" else 1
+        return {"most_attended": {key.decode("utf-8", "replace"): int(c) for key, c in zip(head[0], head[col])},
+                "least_attended": {key.decode("utf-8", "replace"): int(c) for key, c in zip(tail[0], tail[col])},
+                "complete": complete}
+
     def by_hour_of_week(self) -> np.ndarray:
         """Swipes, valid or not, per weekday (Monday first) and UTC hour:
         [7, 24] uint64."""
@@ -487,11 +587,13 @@ class StudentCounts:
         return {d: int(per_day[i]) for d, i in sorted((d, i) for i, d in enumerate(DAY_NAMES)) if per_day[i]}
 
     def insights(self, attended_threshold: int | str | None = None, invalid_threshold: int | str | None = None,
-                 late_threshold: int | str | None = None) -> list:
-        """The reference's per-student and per-day insights (attendance_
-        analysis.py:65-85, :99-118) in its order, each only when its option is
-        on: "Habitual Latecomers" (``track_late``), "Attendance by Day"
-        (``day_profile``), then the two below.  ``data`` is ``{student_id:
+                 late_threshold: int | str | None = None, lecture_k: int | None = 3) -> list:
+        """The reference's insights (attendance_analysis.py:65-118) in its
+        order, each only when its option is on: "Habitual Latecomers"
+        (``track_late``), "Attendance by Day" (``day_profile``), "Lecture
+        Attendance Rankings" (``lecture_counts``: ``lecture_rankings(lecture_k)``,
+        its two lists as ``data``; ``lecture_k=None`` leaves the entry out), then
+        the two below.  ``data`` is ``{student_id:
         estimate}`` of the tracked keys, ``{day name: swipes}`` by day.
         The reference picks its consistent attendees by the median plus the
         standard deviation of every student's count, its latecomers by the
@@ -532,6 +634,13 @@ class StudentCounts:
             out.append({"title": "Attendance by Day",
                         "description": "Distribution of attendance across different days",
                         "data": self.by_day()})
+        if self._lectures is not None and lecture_k is not None:
+            ranks = self.lecture_rankings(lecture_k)
+            out.append({"title": "Lecture Attendance Rankings",
+                        "description": "Most and least attended lectures",
+                        "data": {"most_attended": ranks["most_attended"],
+                                 "least_attended": ranks["least_attended"]},
+                        "complete": ranks["complete"]})
         for title, text, key, thr in (
                 ("Most Consistent Attendees", "Students whose estimated attendance reaches the threshold",
                  self.attended_key, attended_threshold),

@@ -36,9 +36,9 @@ Semantics kept from Redis / RedisBloom / redis-py:
 The client is composed per native unit (csrc/sketch_api_*.cpp): the key table
 (keyspace.py), Bloom (client_bloom.py), Count-Min Sketch (client_cms.py),
 heavy-hitter sets beside a CMS key (client_hh.py), HLL (client_hll.py), the
-fused swipe path (client_swipes.py), the device ingest (client_ingest.py) and
-the time profiles (client_tp.py); commands.py holds the command table, ``bf()`` / ``cms()``
-and the pipeline.  Here: the constructor, the generic key commands and
+fused swipe path (client_swipes.py), the device ingest (client_ingest.py),
+the time profiles (client_tp.py) and the tallies (client_tally.py);
+commands.py holds the command table, ``bf()`` / ``cms()`` and the pipeline.  Here: the constructor, the generic key commands and
 ``execute_command``.
 """
 from __future__ import annotations
@@ -50,6 +50,7 @@ from .client_hh import HhMixin
 from .client_hll import HllMixin
 from .client_ingest import IngestMixin
 from .client_swipes import SwipesMixin
+from .client_tally import TallyMixin
 from .client_tp import TimeProfileMixin
 from .commands import (BFInfo, BloomCommands, CMSCommands, CMSInfo, COMMANDS, Pipeline,  # noqa: F401
                        arity_error, text)
@@ -59,7 +60,8 @@ from .keyspace import (BF_TYPE_NAME, CMS_TYPE_NAME, KIND_TYPE_NAMES, TYPE_NAME_K
                        KeySpace, redis_glob)
 
 
-class SketchClient(BloomMixin, CmsMixin, HhMixin, HllMixin, SwipesMixin, IngestMixin, TimeProfileMixin):
+class SketchClient(BloomMixin, CmsMixin, HhMixin, HllMixin, SwipesMixin, IngestMixin, TimeProfileMixin,
+                   TallyMixin):
     """Drop-in for ``redis.Redis`` on the reference's Bloom + HLL calls."""
 
     def __init__(self, host: str = "localhost", port: int = 6379, db: int = 0,
@@ -72,6 +74,7 @@ class SketchClient(BloomMixin, CmsMixin, HhMixin, HllMixin, SwipesMixin, IngestM
         self._ingest = None  # client_ingest.IngestState, made by the first ingest
         self._hh_init_registry()
         self._tp_init_registry()
+        self._tally_init_registry()
 
     # ------------------------------------------------------------ helpers
     def _ok(self):
@@ -125,6 +128,8 @@ class SketchClient(BloomMixin, CmsMixin, HhMixin, HllMixin, SwipesMixin, IngestM
             self._hh_release(None)
         if self._tp:
             self._tp_release()
+        if self._tally:
+            self._tally_release()
         for key in list(self.keys.kind):
             self.keys.drop(key)
         return True

@@ -46,12 +46,14 @@ class IngestRun:
     """What one ``_ingest_batch`` leaves for a caller that goes on with the
     batch on the device (``StudentCounts.update_messages``): the device
     buffers and parse columns, whether BF.EXISTS ran (``B["valid"]`` holds the
-    answers), and the host-decoded messages -- their indices, encoded ids and
-    timestamps."""
+    answers), and the host-decoded messages -- their indices, encoded ids,
+    timestamps and lectures (the text ``keyspace.day_key`` puts into the key
+    name, encoded)."""
 
-    def __init__(self, B, cols, n, has_bf, host_at, host_ids, host_ts):
+    def __init__(self, B, cols, n, has_bf, host_at, host_ids, host_ts, host_lectures):
         self.B, self.cols, self.n, self.has_bf = B, cols, n, has_bf
         self.host_at, self.host_ids, self.host_ts = host_at, host_ids, host_ts
+        self.host_lectures = host_lectures
 
 
 def _message(blob: memoryview, moffs: np.ndarray, i) -> bytes:
@@ -132,10 +134,11 @@ class IngestMixin:
             self.ctx.call("ske_ingest_swipes", self.keys.fid[bkey], C.c_void_p(B["msgs"].ptr),
                           C.byref(cols), n, C.c_void_p(B["valid"].ptr), C.byref(taken))
             valid[:] = B["valid"].to_host(np.uint8, n).astype(bool)
-        keys, at, ids, tss = self._ingest_host_path(bkey, np.nonzero(dev_status != 0)[0], key_name, valid, status)
+        keys, at, ids, tss, lecs = self._ingest_host_path(bkey, np.nonzero(dev_status != 0)[0], key_name, valid,
+                                                          status)
         if tentative:
             self._ingest_release_unused(B, cols, n, tentative, has_bf, valid, dev_status, keys, at)
-        return valid, status, IngestRun(B, cols, n, has_bf, at, ids, tss)
+        return valid, status, IngestRun(B, cols, n, has_bf, at, ids, tss, lecs)
 
     def _ingest_parse(self, B, blob, moffs, n, day_form) -> IngestCols:
         """Upload the payloads and decode them on the device."""
@@ -180,8 +183,8 @@ class IngestMixin:
     def _ingest_host_path(self, bkey, host, key_name, valid, status):
         """The messages the device did not decode: Python's json / datetime
         semantics, then ``swipes``.  Fills their ``valid`` / ``status``; returns
-        their keys, message indices, encoded ids and times."""
-        ids, keys, at, tss = [], [], [], []
+        their keys, message indices, encoded ids, times and lectures."""
+        ids, keys, at, tss, lecs = [], [], [], [], []
         for m in host:
             try:
                 data, name, ts = key_name(m)
@@ -194,9 +197,10 @@ class IngestMixin:
             keys.append(name)
             at.append(m)
             tss.append(ts)
+            lecs.append(str(data["lecture_id"]).encode())
         if at:
             valid[np.asarray(at)] = self.swipes(bkey, keys, ids)
-        return keys, at, ids, tss
+        return keys, at, ids, tss, lecs
 
     def _ingest_release_unused(self, B, cols, n, tentative, has_bf, valid, dev_status, keys, at):
         """Keys created for this batch that no valid swipe reached are not

@@ -1,7 +1,7 @@
 // sketch_api_ctx.cpp -- libsketch C-ABI (include/sketch.h): the context's
 // lifecycle, options, the sticky error word, streams, host -> device staging,
 // pass timing, the scratch-use ordering and graph capture.  The other
-// subsystems are sketch_api_{bloom,hll,swipes,ingest,cms,hh,tp}.cpp (map: sketch_ctx.h).
+// subsystems are sketch_api_{bloom,hll,swipes,ingest,cms,hh,tp,tally}.cpp (map: sketch_ctx.h).
 #include <stdlib.h>
 #include <string.h>
 
@@ -298,6 +298,10 @@ const char *ske_strerror(int code) {
     case SKE_EHHSPACE: return "ERR heavy-hitter list does not fit the output";
     case SKE_ETPNOSET: return "ERR time profile does not exist";
     case SKE_ETPEXISTS: return "ERR time profile already exists";
+    case SKE_ETALLYNOSET: return "ERR tally does not exist";
+    case SKE_ETALLYEXISTS: return "ERR tally already exists";
+    case SKE_ETALLYCAP: return "ERR tally capacity out of range";
+    case SKE_ETALLYSPACE: return "ERR tally list does not fit the output";
     default: return "ERR unknown";
     }
 }
@@ -348,6 +352,15 @@ int ske_open(int device, ske_ctx **out) {
         c->ingest_grid = int(grid < 65536 ? grid : 65536);
     }
     if (const char *v = getenv("SKE_TP_FORM")) c->tp_form = strtoull(v, nullptr, 10) == 1 ? 1 : 0;
+    if (const char *v = getenv("SKE_TALLY_FORM")) c->tally_form = strtoull(v, nullptr, 10) == 1 ? 1 : 0;
+    if (const char *v = getenv("SKE_TALLY_GRID")) {
+        const unsigned long long grid = strtoull(v, nullptr, 10);
+        c->tally_grid = int(grid < kTallyMaxGrid ? grid : kTallyMaxGrid);
+    }
+    if (const char *v = getenv("SKE_TALLY_LDS_LOG2")) {
+        const unsigned long long l = strtoull(v, nullptr, 10);
+        c->tally_lds_log2 = l < kTallyLdsMinLog2 ? kTallyLdsMinLog2 : l > kTallyLdsMaxLog2 ? kTallyLdsMaxLog2 : int(l);
+    }
     if (hipMalloc(&c->zero16, 64) != hipSuccess || hipMemset(c->zero16, 0, 64) != hipSuccess) {
         ske_close(c);
         return SKE_ENOMEM;
@@ -364,6 +377,7 @@ int ske_close(ske_ctx *c) {
     for (auto &T : c->cms) free_cms(T);
     for (auto &H : c->hh) free_hh(H);
     for (auto &P : c->tp) free_tp(P);
+    for (auto &Y : c->tally) free_tally(Y);
     if (c->regs) (void)hipFree(c->regs);
     if (c->tau) (void)hipFree(c->tau);
     if (c->sig) (void)hipFree(c->sig);

@@ -110,6 +110,43 @@ SKE_HD uint32_t hh_start(uint64_t digest, uint32_t capacity_log2) {
     return uint32_t(digest) & ((1u << capacity_log2) - 1);
 }
 
+// Tallies (sketch_tally.hip): a key of at most 32 bytes is held as four
+// little-endian words, zero padded.  Its claim word is its digest -- the general
+// item hash (MurmurHash64A of the key bytes, the Bloom seed; the length enters
+// through the seed word, so b"A" and b"A\0" differ), 0 (the empty slot) mapped
+// to 1 -- and its probe path starts at the digest's low bits.
+constexpr uint32_t kTallyKeyWords = 4;
+SKE_HD uint64_t tally_digest(const uint64_t (&w)[kTallyKeyWords], uint32_t len) {
+    uint64_t h = kBloomSeed ^ (uint64_t(len) * kMurmurM);
+    const uint32_t nblk = len >> 3;
+    uint64_t tail = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kTallyKeyWords; j++) {
+        if (j < nblk)
+            h = mm_block(h, w[j]);
+        else if (j == nblk)
+            tail = w[j];
+    }
+    if (len & 7) {
+        h ^= tail;
+        h *= kMurmurM;
+    }
+    h = mm_final(h);
+    return h ? h : 1;
+}
+SKE_HD uint32_t tally_start(uint64_t digest, uint32_t capacity_log2) {
+    return uint32_t(digest) & ((1u << capacity_log2) - 1);
+}
+// The order of a listing: count descending, then key bytes ascending (a prefix
+// before its extensions: the padding is zero, so the padded bytes decide all
+// but that, and there the shorter key is first).  ka, kb: 32 padded bytes.
+inline bool tally_before(uint64_t ca, const uint8_t *ka, uint32_t la, uint64_t cb, const uint8_t *kb, uint32_t lb) {
+    if (ca != cb) return ca > cb;
+    for (uint32_t j = 0; j < 8 * kTallyKeyWords; j++)
+        if (ka[j] != kb[j]) return ka[j] < kb[j];
+    return la < lb;
+}
+
 // MurmurHash64A of an item of at most 8 bytes held in w (zero padded).
 SKE_HD uint64_t murmur_short(uint64_t w, uint32_t len, uint64_t seed) {
     uint64_t h = seed ^ (uint64_t(len) * kMurmurM);

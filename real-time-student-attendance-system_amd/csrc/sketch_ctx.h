@@ -11,6 +11,7 @@
 //   sketch_api_cms.cpp     Count-Min Sketch tables: init, add, query, merge, export / import
 //   sketch_api_hh.cpp      heavy-hitter sets beside a table: init, track, list, stats, select
 //   sketch_api_tp.cpp      time profiles (weekday x hour counters): init, add, read / import
+//   sketch_api_tally.cpp   tallies (exact event counts per key): init, add, query, list, top, import
 // A helper used by one unit is static there; what crosses units is declared here.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -68,6 +69,15 @@ struct Tp {
     unsigned long long *counts = nullptr;  // device
 };
 
+// one tally (base == nullptr: the tid is free); one allocation: a 64-byte head
+// (used, overflow, taken, the dropped totals), then the claim words, the key
+// words, the two counters and the lengths
+struct Tally {
+    uint8_t *base = nullptr;
+    size_t bytes = 0;
+    uint32_t log2 = 0;
+};
+
 struct Staged {
     const uint8_t *bytes = nullptr;
     const uint32_t *offs = nullptr;
@@ -106,6 +116,15 @@ struct ske_ctx {
     // lane); for small-shape tests and A/B timing, neither changes a result
     int tp_grid = 0;
     int tp_form = 0;
+    std::vector<ske::Tally> tally;  // by tid (sized on first use)
+    bool tally_ready = false;       // tally_setup() done (first ske_tally_init)
+    // a tally add's form (SKE_TALLY_FORM, read by ske_open: 0 a hash table in
+    // each workgroup's LDS first, 1 one insert-or-add in memory per item), form
+    // 0's workgroups (SKE_TALLY_GRID; 0: one per CU) and the slots of its LDS
+    // table (SKE_TALLY_LDS_LOG2); for small-shape tests and A/B timing, none changes a result
+    int tally_form = 0;
+    int tally_grid = 0;
+    int tally_lds_log2 = ske::kTallyLdsMaxLog2;
     // workgroups of ske_ingest_times / ske_ingest_dense (SKE_INGEST_GRID, read by
     // ske_open; 0: the ingest kernels' launch shape); for small-shape tests, changes no result
     int ingest_grid = 0;
@@ -267,6 +286,9 @@ void free_hh(Hh &H);
 
 // ---- sketch_api_tp.cpp
 void free_tp(Tp &P);
+
+// ---- sketch_api_tally.cpp
+void free_tally(Tally &Y);
 
 // ---- sketch_api_swipes.cpp
 bool use_lds(const ske_ctx *c, const ChainDev &ch);

@@ -303,6 +303,56 @@ constexpr unsigned kTpMaxGrid = 4096;
 // 1: one LDS atomic per lane, always.  grid: workgroups (at most kTpMaxGrid; fewer for a small n)
 hipError_t launch_tp_add(const TpArgs &A, int form, unsigned grid, hipStream_t st);
 
+// sketch_tally.hip -- tallies: exact event counts per key (a byte string of at
+// most kTallyKeyBytes), an insert-or-add open-addressing table
+constexpr uint32_t kTallyKeyBytes = 8 * kTallyKeyWords;  // SKE_TALLY_KEY_BYTES
+constexpr uint32_t kTallyMaxProbes = 128;  // slots one insert-or-add looks at (SKE_TALLY_MAX_PROBES)
+constexpr uint32_t kTallyLoadDen = 2;      // new claims stop at capacity / kTallyLoadDen (SKE_TALLY_LOAD_DEN)
+constexpr int kTallyLdsMinLog2 = 4;        // form 0: slots of a workgroup's LDS table, 2^4 ..
+constexpr int kTallyLdsMaxLog2 = 12;       //   2^12 (20 bytes a slot: 80 KiB of the CU's 160)
+constexpr unsigned kTallyMaxGrid = 4096;
+struct TallyTab {
+    unsigned long long *claim;   // per slot: the key's digest (tally_digest), 0 = empty
+    uint64_t *keys;              // per slot: the key's four words, written by the claim's winner
+    unsigned long long *events;  // per slot: items counted
+    unsigned long long *valid;   // per slot: of those, the ones whose mask byte was 1
+    uint32_t *len;               // per slot: the key's length
+    unsigned int *used;          // slots claimed
+    unsigned int *overflow;      // sticky: an item was refused (or its key too long)
+    unsigned long long *taken;   // items looked at
+    unsigned long long *dropped_events, *dropped_valid;  // the counts of refused items
+    uint32_t mask;               // capacity - 1
+    uint32_t limit;              // capacity / kTallyLoadDen
+};
+// where a batch's keys are: kind 0 packed (key i = bytes[offs[i] .. offs[i + 1])),
+// 1 fixed width (bytes + i * fixed_w), 2 spans (bytes[start[i] .. start[i] +
+// len[i]), taken only when status is null or status[i] == 0), 3 a listing
+// (32 padded bytes a key at bytes + 32 i, len[i]; item i counts ev[i] / va[i])
+struct TallyItems {
+    int kind;
+    const uint8_t *bytes;
+    const uint32_t *offs;    // kind 0: offsets; kind 2: starts
+    const uint32_t *len;     // kind 2, 3
+    const uint8_t *status;   // kind 2, may be null
+    const uint8_t *mask;     // may be null: no item is valid
+    const uint64_t *ev, *va; // kind 3
+    uint32_t fixed_w, n;
+    unsigned int *toolong;   // may be null: set when a key is longer than kTallyKeyBytes
+};
+hipError_t tally_setup();
+// form 0: one LDS table of 2^lds_log2 slots per workgroup, flushed at the end;
+// 1: one insert-or-add in memory per item.  grid: workgroups of form 0 (at most kTallyMaxGrid)
+hipError_t launch_tally_add(const TallyTab &T, const TallyItems &I, int form, unsigned grid, int lds_log2, int cus,
+                            hipStream_t st);
+// ev[i], va[i] = the counters of item i's key (0, 0 when absent or too long)
+hipError_t launch_tally_query(const TallyTab &T, const TallyItems &I, uint64_t *ev, uint64_t *va, int cus,
+                              hipStream_t st);
+// entries with events >= min_events, unordered: entry j < min(*out_n, cap) in
+// out_keys[4j..], out_len[j], out_ev[j], out_va[j]; *out_n (zeroed by the caller) counts all that pass
+hipError_t launch_tally_list(const TallyTab &T, uint64_t min_events, uint32_t cap, uint64_t *out_keys,
+                             uint32_t *out_len, uint64_t *out_ev, uint64_t *out_va, unsigned int *out_n,
+                             hipStream_t st);
+
 // sketch_hll_fmt.hip -- HLL keys as Redis "HYLL" strings, one key per workgroup
 // (DESIGN.md section 14); the opcode rules are sketch_hll_fmt.h's
 // sizes[i] = length of key i's string (slots == nullptr: keys 0 .. nkeys - 1);
@@ -421,6 +471,12 @@ enum StageSlot : int {
     kStgHllFmtBlob,    // ske_hll_dump: the strings on their way to the host
     kStgHllFmtStatus,  // ske_hll_load: a status byte per key on its way to the host
     kStgHllFmtFlag,    // ske_hll_load: the offsets-decrease word, then the any-string-refused word
+    kStgTallyFlag,     // ske_tally_add: the too-long word | ske_tally_list / ske_tally_top: the count of entries that pass
+    kStgTallyMask,     // ske_tally_add: a mask byte per item
+    kStgTallyKeys,     // ske_tally_list / ske_tally_top: the entries' key words | ske_tally_import: the keys,
+    kStgTallyLen,      //   lengths,
+    kStgTallyEv,       //   events (also ske_tally_query's reply on its way to the host),
+    kStgTallyVa,       //   valid (likewise)
     kStageSlotCount
 };
 

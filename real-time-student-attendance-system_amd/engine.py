@@ -14,7 +14,7 @@ import gc
 import numpy as np
 
 from ._lib import (CmsInfo, Context, GenParams, HhInfo, HhStats, IngestDense, SKE_HH_ID_BYTES, SKE_HLL_DUMP_CARD,
-                   SKE_MEM_DEVICE, SKE_TP_BINS)
+                   SKE_MEM_DEVICE, SKE_MEM_HOST, SKE_TALLY_KEY_BYTES, SKE_TP_BINS, TallyInfo)
 from . import synthetic
 
 PASS_KINDS = 9  # SKE_PASS_KINDS (include/sketch.h)
@@ -125,6 +125,86 @@ def tp_import(ctx: Context, tid: int, counts) -> None:
     if a.size != SKE_TP_BINS:
         raise ValueError(f"a time profile has {SKE_TP_BINS} counters")
     ctx.call("ske_tp_import", int(tid), a.ctypes.data_as(C.c_void_p))
+
+
+def tally_info(ctx: Context, tid: int) -> dict:
+    """ske_tally_info: capacity, used, the sticky overflow word, the items
+    looked at and the counts of those that were not grouped."""
+    info = TallyInfo()
+    ctx.call("ske_tally_info", int(tid), C.byref(info))
+    return {k: int(getattr(info, k)) for k in ("capacity", "used", "overflow", "taken", "dropped_events",
+                                               "dropped_valid")}
+
+
+def _tally_rows(keys, lens, events, valid, k):
+    return ([keys[i, :lens[i]].tobytes() for i in range(k)], events[:k].copy(), valid[:k].copy())
+
+
+def tally_list(ctx: Context, tid: int, min_events: int = 0, room: int | None = None):
+    """ske_tally_list: ``(keys, events, valid, complete)`` -- the entries of
+    tally ``tid`` with at least ``min_events`` events, the keys as bytes, sorted
+    by events descending, then key bytes ascending; their counters (u64), and
+    whether every count is exact.  ``room``: entries the output holds (default:
+    the tally's ``used``, always enough)."""
+    if room is None:
+        room = tally_info(ctx, tid)["used"]
+    room = max(int(room), 1)
+    keys = np.zeros((room, SKE_TALLY_KEY_BYTES), np.uint8)
+    lens = np.zeros(room, np.uint32)
+    events, valid = np.zeros(room, np.uint64), np.zeros(room, np.uint64)
+    n, complete = C.c_uint64(0), C.c_int(1)
+    ctx.call("ske_tally_list", int(tid), int(min_events), keys.ctypes.data_as(C.c_void_p),
+             lens.ctypes.data_as(C.c_void_p), events.ctypes.data_as(C.c_void_p), valid.ctypes.data_as(C.c_void_p),
+             room, C.byref(n), C.byref(complete))
+    return _tally_rows(keys, lens, events, valid, int(n.value)) + (bool(complete.value),)
+
+
+def tally_top(ctx: Context, tid: int, k: int = 3, by: int = 0):
+    """ske_tally_top: ``(head, tail, complete)`` -- the first and the last
+    ``k`` entries of the listing's order (``by`` 0: by events, 1: by valid), each
+    end as ``(keys, events, valid)``; the tail in list order."""
+    k = int(k)
+    ends = []
+    for _ in range(2):
+        ends.append((np.zeros((max(k, 1), SKE_TALLY_KEY_BYTES), np.uint8), np.zeros(max(k, 1), np.uint32),
+                     np.zeros(max(k, 1), np.uint64), np.zeros(max(k, 1), np.uint64)))
+    n, complete = C.c_uint64(0), C.c_int(1)
+    ctx.call("ske_tally_top", int(tid), k, int(by), *[a.ctypes.data_as(C.c_void_p) for e in ends for a in e],
+             C.byref(n), C.byref(complete))
+    m = int(n.value)
+    return _tally_rows(*ends[0], m), _tally_rows(*ends[1], m), bool(complete.value)
+
+
+def tally_query(ctx: Context, tid: int, buf: np.ndarray, offs: np.ndarray):
+    """ske_tally_query over a packed host batch: ``(events, valid)``, u64 per
+    key; 0, 0 for a key the tally does not hold."""
+    n = len(offs) - 1
+    events, valid = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    if n > 0:
+        b = np.ascontiguousarray(buf, np.uint8)
+        o = np.ascontiguousarray(offs, np.uint32)
+        ctx.call("ske_tally_query", int(tid), b.ctypes.data_as(C.c_void_p), o.ctypes.data_as(C.c_void_p), n,
+                 events.ctypes.data_as(C.c_void_p), valid.ctypes.data_as(C.c_void_p), SKE_MEM_HOST)
+    return events, valid
+
+
+def tally_import(ctx: Context, tid: int, keys, events, valid) -> None:
+    """ske_tally_import: insert-or-add of a listing (keys as bytes)."""
+    n = len(keys)
+    if not (len(events) == n and len(valid) == n):
+        raise ValueError("one events and one valid count per key")
+    if n == 0:
+        return
+    if max(len(k) for k in keys) > SKE_TALLY_KEY_BYTES:
+        raise ValueError(f"a tally key has at most {SKE_TALLY_KEY_BYTES} bytes")
+    kb = np.zeros((n, SKE_TALLY_KEY_BYTES), np.uint8)
+    for i, k in enumerate(keys):
+        kb[i, :len(k)] = np.frombuffer(k, np.uint8)
+    lens = np.asarray([len(k) for k in keys], np.uint32)
+    ev = np.ascontiguousarray(events, dtype=np.uint64)
+    va = np.ascontiguousarray(valid, dtype=np.uint64)
+    ctx.call("ske_tally_import", int(tid), kb.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
+             ev.ctypes.data_as(C.c_void_p), va.ctypes.data_as(C.c_void_p), n)
 
 
 class SweBatch(C.Structure):
@@ -440,6 +520,51 @@ class SketchEngine:
         self.ctx.call("ske_tp_add_async", int(tid), C.c_void_p(epoch.ptr), int(n),
                       C.c_void_p(mask.ptr) if mask else None, int(want), int(late_from),
                       C.c_void_p(late.ptr) if late else None)
+
+    # ---- tallies: exact event counts per key
+    def tally_init(self, tid: int, capacity_log2: int):
+        self.ctx.call("ske_tally_init", int(tid), int(capacity_log2))
+
+    def tally_free(self, tid: int):
+        self.ctx.call("ske_tally_free", int(tid))
+
+    def tally_reset(self, tid: int):
+        self.ctx.call("ske_tally_reset", int(tid))
+
+    def tally_info(self, tid: int) -> dict:
+        return tally_info(self.ctx, tid)
+
+    def tally_add(self, tid: int, b: DeviceBatch, mask: DeviceBuffer | None = None):
+        """One resident batch of keys into tally ``tid``: every key counts one
+        event, and one valid where its ``mask`` byte is 1.  Only enqueued
+        (ske_tally_add_fixed_async for a fixed-width batch, else
+        ske_tally_add_packed_async; capturable; ``sync()`` waits)."""
+        m = C.c_void_p(mask.ptr) if mask else None
+        if b.width > 0:
+            self.ctx.call("ske_tally_add_fixed_async", int(tid), C.c_void_p(b.bytes.ptr), b.width, b.n, m)
+        else:
+            self.ctx.call("ske_tally_add_packed_async", int(tid), C.c_void_p(b.bytes.ptr), C.c_void_p(b.offs.ptr),
+                          b.n, m)
+
+    def tally_add_spans(self, tid: int, msgs: DeviceBuffer, start: DeviceBuffer, length: DeviceBuffer, n: int,
+                        status: DeviceBuffer | None = None, mask: DeviceBuffer | None = None):
+        """ske_tally_add_spans_async: key i = ``msgs[start[i] .. start[i] +
+        length[i])``, taken where ``status`` (if any) is 0.  Only enqueued."""
+        self.ctx.call("ske_tally_add_spans_async", int(tid), C.c_void_p(msgs.ptr), C.c_void_p(start.ptr),
+                      C.c_void_p(length.ptr), int(n), C.c_void_p(status.ptr) if status else None,
+                      C.c_void_p(mask.ptr) if mask else None)
+
+    def tally_list(self, tid: int, min_events: int = 0):
+        return tally_list(self.ctx, tid, min_events)
+
+    def tally_top(self, tid: int, k: int = 3, by: int = 0):
+        return tally_top(self.ctx, tid, k, by)
+
+    def tally_query(self, tid: int, buf: np.ndarray, offs: np.ndarray):
+        return tally_query(self.ctx, tid, buf, offs)
+
+    def tally_import(self, tid: int, keys, events, valid):
+        tally_import(self.ctx, tid, keys, events, valid)
 
     # ---- ingest: the decoded messages' times, and the decoded messages as one packed batch
     def ingest_times(self, msgs: DeviceBuffer, cols, n: int, epoch: DeviceBuffer):

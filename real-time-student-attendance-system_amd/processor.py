@@ -115,19 +115,39 @@ class AttendanceProcessor:
             self.acked += len(rows)
             if self.counts is not None:  # the rows the reference inserts, invalid ones included
                 buf, offs = pack(ids)
+                lectured = getattr(self.counts, "counts_lectures", False)
                 self.counts.count_packed(buf, offs, valid,
-                                         [r["timestamp"] for r in rows] if self.counts.timed else None)
+                                         [r["timestamp"] for r in rows] if self.counts.timed else None,
+                                         **({"lectures": [r["lecture_id"] for r in rows]} if lectured else {}))
         return rows
 
-    def insights(self, keys: Sequence[str] | None = None, k: int = 3, **thresholds) -> list:
+    def insights(self, keys: Sequence[str] | None = None, k: int = 3, rank_by: str | None = None,
+                 **thresholds) -> list:
         """attendance_analysis.py:65-118 in its order: ``counts.insights(
-        **thresholds)`` and, when ``keys`` (lecture-day HLL keys) are given,
-        "Lecture Attendance Rankings" (``lecture_rankings(keys, k)``, :87-97)
-        at its place, after the per-day entries and before the per-student
-        lists of :99-118."""
+        **thresholds)`` with "Lecture Attendance Rankings" (:87-97) at its
+        place, after the per-day entries and before the per-student lists of
+        :99-118, in one of the two forms README.md:179 allows, never both:
+          - ``rank_by="events"``, or no ``keys`` and ``counts`` has a lecture
+            tally (``lecture_counts``): the reference's own form, rows per
+            lecture (``counts.lecture_rankings(k)``), no key list needed;
+          - ``keys`` (lecture-day HLL keys) with ``rank_by`` None or
+            ``"unique"``: the unique counts by PFCOUNT (``lecture_rankings(keys,
+            k)``);
+          - neither: no such entry."""
         if self.counts is None:
             raise ValueError("insights need a StudentCounts (counts=)")
-        out = self.counts.insights(**thresholds)
+        if rank_by not in (None, "unique", "events"):
+            raise ValueError('rank_by is None, "unique" or "events"')
+        lectured = getattr(self.counts, "counts_lectures", False)
+        if rank_by == "events" and not lectured:
+            raise ValueError('rank_by="events" needs a StudentCounts with lecture_counts')
+        if rank_by == "unique" and keys is None:
+            raise ValueError('rank_by="unique" needs the lecture-day keys')
+        by_events = rank_by == "events" or (keys is None and lectured)
+        if by_events:
+            return self.counts.insights(lecture_k=k, **thresholds)
+        # the PFCOUNT entry takes the place of the tally's
+        out = self.counts.insights(**(dict(thresholds, lecture_k=None) if lectured else thresholds))
         if keys is not None:
             at = sum(1 for i in out if i["title"] in ("Habitual Latecomers", "Attendance by Day"))
             out.insert(at, {"title": "Lecture Attendance Rankings",
@@ -159,13 +179,26 @@ class AttendanceProcessor:
         keys come from the key table's stem index (KeySpace.day_keys, kept
         by every key creation / DEL, so a fresh processor on the same store
         answers the same without scanning every key; a lecture id that is a
-        prefix of another, e.g. 'A' and 'A:B', keeps its own keys)."""
+        prefix of another, e.g. 'A' and 'A:B', keeps its own keys).  When
+        ``counts`` has a lecture tally the dict also carries
+        ``attendance_record_count`` and ``invalid_record_count``, the lecture's
+        rows valid or not and the invalid ones, over every day."""
+        out = {"unique_attendees": self._unique_attendees(lecture_id, day)}
+        if getattr(self.counts, "counts_lectures", False):
+            # the reference's attendance_records (:154-165), rows per lecture over
+            # every day: the tally is keyed by lecture alone
+            ev, va = self.counts.lecture_events([lecture_id])
+            out["attendance_record_count"] = int(ev[0])
+            out["invalid_record_count"] = int(ev[0]) - int(va[0])
+        return out
+
+    def _unique_attendees(self, lecture_id: str, day: str | None) -> int:
         prefix = self.config.hll_key_prefix
         if self.config.hll_key_form == "code":
             key = f"{prefix}{lecture_id}" + (f":{day}" if day else "")
-            return {"unique_attendees": self.redis_client.pfcount(key)}
+            return self.redis_client.pfcount(key)
         if day is not None:
-            return {"unique_attendees": self.redis_client.pfcount(f"{prefix}{lecture_id}:{day}")}
+            return self.redis_client.pfcount(f"{prefix}{lecture_id}:{day}")
         stem = f"{prefix}{lecture_id}"
         index = getattr(self.redis_client, "day_keys", None)
         if callable(index):  # SketchClient: the key table's stem index
@@ -174,7 +207,7 @@ class AttendanceProcessor:
             pat = glob_escape(stem)
             keys = list(self.redis_client.scan_iter(match=pat + ":" + "[0-9]" * 4 + "-" + "[0-9]" * 2 + "-" +
                                                      "[0-9]" * 2, _type="string"))
-        return {"unique_attendees": self.redis_client.pfcount(*keys) if keys else 0}
+        return self.redis_client.pfcount(*keys) if keys else 0
 
 
 def glob_escape(text: str) -> str:
