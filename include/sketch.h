@@ -688,7 +688,11 @@ int ske_swipes_variant(ske_ctx *ctx, uint32_t fid);
  * which a batch is segmented, x100, default 600, doubled for a slab of at
  * most 192 MB), "seg_dense_min" (records per window line at which a window
  * is staged in LDS, x100), "seg_klog" (0..3: keys per window 1, 2, 4, 8;
- * default 1), "seg_b1" (-1 auto, 0..9: 2^b1 level-1 buckets).  Any other
+ * default 1), "seg_b1" (-1 auto, 0..9: 2^b1 level-1 buckets), "seg_floor"
+ * (1, the default: records that cannot raise a register, because their rank
+ * is at or under the minimum of their key's registers, are dropped before the
+ * window pass; 0: never), "seg_hot_min" (arrivals per key and window pass from
+ * which a window's minimum is derived, default 4096, up to 2^31).  Any other
  * name or an out-of-range value: SKE_EINVAL.  None changes an answer or a
  * register. */
 int ske_set_option(ske_ctx *ctx, const char *name, int64_t value);
@@ -707,6 +711,11 @@ int ske_set_option(ske_ctx *ctx, const char *name, int64_t value);
  * reset != 0 zeroes the sums after reading. */
 #define SKE_PASS_KINDS 9
 int ske_pass_times(ske_ctx *ctx, double *ms_out, uint64_t *count_out, int reset);
+/* The segmented PFADD's floor statistics since the last read (waits for the
+ * context's stream): out[0] key windows whose register minimum was derived,
+ * out[1] level-1 records the level-2 sort saw, out[2] those it dropped as
+ * unable to raise a register.  All zero with "seg_floor" 0. */
+int ske_seg_floor_stats(ske_ctx *ctx, uint64_t out[3]);
 
 /* ---- ingest: JSON event decode + key-slot resolution ----
  * The reference decodes each Pulsar payload on the CPU (attendance_processor.py

@@ -466,6 +466,18 @@ int ske_pass_times(ske_ctx *c, double *ms, uint64_t *count, int reset) {
     return SKE_OK;
 }
 
+int ske_seg_floor_stats(ske_ctx *c, uint64_t out[3]) {
+    if (!c || !out) return SKE_EINVAL;
+    out[0] = out[1] = out[2] = 0;
+    void *p = scratch_peek(c->scratch, kScrSegFstat);
+    if (!p) return SKE_OK;  // no segmented batch with floors yet
+    if (c->xr.stream && c->xr.stream != c->st) HIPCHK(c, hipStreamSynchronize(c->xr.stream));
+    HIPCHK(c, hipMemcpyAsync(out, p, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemsetAsync(p, 0, 3 * sizeof(uint64_t), c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SKE_OK;
+}
+
 int ske_device_alloc(ske_ctx *c, uint64_t bytes, void **out) {
     if (!c || !out) return SKE_EINVAL;
     hipError_t e = hipMalloc(out, bytes ? bytes : 16);
@@ -516,6 +528,10 @@ int ske_set_option(ske_ctx *c, const char *name, int64_t value) {
         {"seg_klog", 0, 3, [](ske_ctx *x, int64_t v) { x->seg.klog = int(v); }},
         // segmented PFADD: 2^b1 level-1 buckets, -1 auto
         {"seg_b1", -1, 9, [](ske_ctx *x, int64_t v) { x->seg.b1 = int(v); }},
+        // segmented PFADD: 1 D drops the records under their key's floor, 0 never
+        {"seg_floor", 0, 1, [](ske_ctx *x, int64_t v) { x->seg.floor = int(v); }},
+        // arrivals per key and window-pass group from which a window is hinted for a floor
+        {"seg_hot_min", 0, int64_t(1) << 31, [](ske_ctx *x, int64_t v) { x->seg.hot_min = uint32_t(v); }},
         // blocks of the short-id LDS K1 (0: one per CU)
         {"k1_grid", 0, 65535, [](ske_ctx *x, int64_t v) { x->k1_grid = int(v); }},
         // 0: many-batch calls launch K1 per batch

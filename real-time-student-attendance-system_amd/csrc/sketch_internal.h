@@ -163,7 +163,8 @@ struct Scratch;
 bool part_supported(const ChainDev &ch);
 // The segmented PFADD (k_seg_*, the pass C of one-link chains when a batch's
 // register updates are dense in the slab) -- options "hll_seg" (mode),
-// "seg_density" and "seg_dense_min" (x100), "seg_klog".
+// "seg_density" and "seg_dense_min" (x100), "seg_klog", "seg_floor" and
+// "seg_hot_min" (the per-key floors, sketch_seg.hip).
 struct SegOpts {
     int mode = -1;                  // -1 auto, 0 never (pass C), 1 whenever the chain and slab allow
     uint32_t density_x100 = 600;    // auto: a batch's swipes per 128-B line of the slab, x100 (x2 when the
@@ -171,6 +172,8 @@ struct SegOpts {
     uint32_t dense_min_x100 = 100;  // a window is staged in LDS from this many records per line, x100
     int klog = 1;                   // keys per window: 2^klog (16 KiB each; 0..3)
     int b1 = -1;  // option "seg_b1": 2^b1 level-1 buckets (-1: auto, seg_plan)
+    int floor = 1;               // 1: D drops the records no register can rise from (per-key floors); 0: never
+    uint32_t hot_min = 4096;     // a window is hinted for a floor from this many arrivals per key and group
 };
 // sizes the context scratch for batches of up to n swipes (no launch)
 // sub: swipes per sub-batch of the three passes (0: the default, 2^25 = kPSubDefault)
@@ -375,7 +378,7 @@ hipError_t launch_hll_fmt_offs_check(const uint32_t *offs, uint32_t n, unsigned 
 
 // sketch_order.hip -- order-exact paths (replies that depend on item order)
 struct Scratch;  // growable device scratch, owned by the context
-constexpr int kScratchSlots = 48;
+constexpr int kScratchSlots = 52;
 
 // Every slot of the context scratch, by owner (who sizes it) and user.  The
 // numbers carry no meaning beyond identity; a slot belongs to exactly one of
@@ -439,7 +442,10 @@ enum ScratchSlot : int {
     kScrSegQ,          //   the window pass's queue word,
     kScrSegQitems,     //   queue entries,
     kScrSegMlist,      //   cut windows,
-    kScrSegCopies,     //   their window copies
+    kScrSegCopies,     //   their window copies,
+    kScrSegFloor,      //   the per-key floors of a group (a byte per key slot, bucket-major),
+    kScrSegHot,        //   the hint map (a header and a byte per window; survives between calls),
+    kScrSegFstat,      //   the floor statistics (ske_seg_floor_stats)
     // -- rt
     kScrRouteHist,     // ske_route_swipes, ske_route_swipes_cap_async: per-block histogram,
     kScrRouteTot,      // ske_route_swipes: the owners' totals
@@ -483,6 +489,10 @@ enum StageSlot : int {
 Scratch *scratch_new();
 void scratch_delete(Scratch *s);
 void *scratch_get(Scratch *s, ScratchSlot slot, size_t bytes, hipError_t *err);
+// the same for a slot whose content is kept from call to call: a buffer newly
+// allocated (or grown) is handed out zeroed
+void *scratch_get_zeroed(Scratch *s, ScratchSlot slot, size_t bytes, hipError_t *err);
+void *scratch_peek(const Scratch *s, ScratchSlot slot);  // the slot's buffer as it stands (may be null)
 void scratch_set_recording(Scratch *s, bool on);  // slots handed out now get pinned
 void scratch_unpin(Scratch *s);                    // every graph freed: slots may grow
 

@@ -58,6 +58,23 @@ void *scratch_get(Scratch *s, ScratchSlot slot, size_t bytes, hipError_t *err) {
     return s->p[slot];
 }
 
+void *scratch_get_zeroed(Scratch *s, ScratchSlot slot, size_t bytes, hipError_t *err) {
+    const void *was = s->p[slot];
+    const size_t cap = s->cap[slot];
+    void *p = scratch_get(s, slot, bytes, err);
+    // (never inside a capture: a pinned slot does not grow)
+    if (p && (p != was || s->cap[slot] != cap)) {
+        const hipError_t e = hipMemset(p, 0, s->cap[slot]);
+        if (e != hipSuccess) {
+            *err = e;
+            return nullptr;
+        }
+    }
+    return p;
+}
+
+void *scratch_peek(const Scratch *s, ScratchSlot slot) { return s->p[slot]; }
+
 void scratch_free_all(Scratch *s) {
     for (int i = 0; i < kScratchSlots; i++)
         if (s->p[i]) (void)hipFree(s->p[i]);

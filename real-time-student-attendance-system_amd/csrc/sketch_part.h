@@ -194,7 +194,15 @@ struct SegArgs {
     uint32_t kstat;   // chunk c < kstat of bucket h sits in slot h * kstat + c; later chunks take
                       // slots nb1 * kstat + (counter), named in ctab
     unsigned int *err;  // the call's error word (D: bit 8, more chunks than maxch rows)
+    // the per-key floors (sketch_seg.hip, k_seg_floor); all null with option "seg_floor" 0
+    uint8_t *floor;   // [nb1 << s1] the group's floor of key slot (W & (nb1 - 1)) << s1 | slot-in-bucket
+    uint8_t *hot;     // kSegHotHdr header bytes (the plan the map belongs to), then a hint byte per window
+    unsigned long long *fstat;  // [0] windows floored, [1] records D saw, [2] records D dropped
+    uint32_t hot_min;  // arrivals per key and group from which E hints a window
 };
+constexpr uint32_t kSegHotHdr = 16;          // the hint map's header: nwin, klog, b1, kSegHotMagic
+constexpr uint32_t kSegHotMagic = 0x686f7431u;
+constexpr uint32_t kSegHotAge = 4;           // groups a hint outlives E's last visit
 
 // the fail-list instantiation: one link of k = 11 (C3/C5's filter), slice
 // pairs (the sink pair must fit k_part_a3<11, 2048>'s counters)

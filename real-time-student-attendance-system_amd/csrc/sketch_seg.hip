@@ -34,6 +34,21 @@
 //                   raised there (LDS CAS; registers only grow), and the
 //                   lines that rose are stored back; a sparse window raises
 //                   its records in place (pre-check load + CAS, as pass C).
+//   F  (k_seg_floor) per window-pass group, before its first C1: the byte
+//                   minimum (floor) of every hinted key's registers, from the
+//                   slab as it stands; D drops the records at or under their
+//                   key's floor, which can raise nothing (see k_seg_floor).
+//                   Measured at the 2^28 default step against the build
+//                   without it (profiles/r21_ab_seg_floor.txt): step 8.40-8.44
+//                   -> 8.13-8.15 ms, E 1.05 -> 0.82, D 0.059 -> 0.053 per
+//                   sub-batch, the floor pass +0.03 ms per step, 50.4 % of the
+//                   timed steps' records dropped.
+//                   Measured and removed: the same test in C1 before its
+//                   store (a 1-byte gather from the floor table per valid
+//                   swipe; 84 VGPRs' worth in an 80-VGPR kernel, 4 spilled):
+//                   C1 0.111 -> 0.148 ms per sub-batch against D 0.053 ->
+//                   0.036 and E 0.81 -> 0.76, step 8.08-8.13 -> 8.21-8.23 ms,
+//                   same registers (three alternations, same file).
 #include <algorithm>
 #include <type_traits>
 
@@ -318,6 +333,105 @@ __global__ void __launch_bounds__(T, SegC1<T>::WPE) k_seg_c1(const PartArgs A, c
     }
 }
 
+// The per-key floors.  A record (slot, register, rank) matters only if rank >
+// register.  A key that has seen many distinct ids has every one of its
+// 16 384 registers at or above some value f, its floor, and a record of rank
+// <= f for that key raises nothing: D drops it (P(rank <= f) = 1 - 2^-f), so
+// it is neither written to r2 nor read and compared by E.
+// Exact because the floor is never a cached fact about the registers:
+// k_seg_floor derives it from the slab as it stands at the start of every
+// window-pass group, registers only rise until the group's E has run, and the
+// next group derives it again -- whatever wrote the slab before the call
+// (ske_hll_clear, an import, a load, growth, a store through ske_hll_slab's
+// pointer) is seen.  No floor survives a group.
+// Deriving a floor reads the key's 16 KiB, so only hinted windows get one
+// (the others: floor 0, nothing dropped).  The hint map -- a byte per window,
+// kept from call to call behind a header naming the plan (nwin, klog, b1) it
+// belongs to -- decides cost only, never a result: E1 sets a window's byte to
+// kSegHotAge when (kept records << the window's floor), its estimate of the
+// arrivals before the filter, reaches hot_min per key (a cut window: always),
+// clears it under half of that, and k_seg_floor counts it down by one per
+// group, so a window E has not seen a record of for kSegHotAge groups stops
+// costing reads.  A map whose header names another plan counts as all zero:
+// E1 then writes every window's byte and M the header.
+__device__ __forceinline__ bool seg_hot_valid(const SegArgs &S) {
+    const uint32_t *h = reinterpret_cast<const uint32_t *>(S.hot);
+    return h[0] == S.nwin && h[1] == S.klog && h[2] == S.b1 && h[3] == kSegHotMagic;
+}
+// the floor table's entry of key k of window w (bucket-major: D's floors of
+// one bucket are contiguous, indexed by the record's slot-in-bucket)
+__device__ __forceinline__ uint32_t seg_floor_at(const SegArgs &S, uint32_t w, uint32_t k) {
+    return ((w & (S.nb1 - 1)) << S.s1) | ((w >> S.b1) << S.klog) | k;
+}
+__device__ __forceinline__ part_u32x4 seg_min16(part_u32x4 a, part_u32x4 b) {
+    typedef unsigned char u8x16 __attribute__((ext_vector_type(16)));
+    return __builtin_bit_cast(part_u32x4,
+                              __builtin_elementwise_min(__builtin_bit_cast(u8x16, a), __builtin_bit_cast(u8x16, b)));
+}
+// the least of a wave's 64 x 16 bytes, in every lane
+__device__ __forceinline__ uint32_t seg_wave_min8(part_u32x4 v) {
+    uint32_t x = 0xffu;
+#pragma unroll
+    for (uint32_t c = 0; c < 4; c++)
+#pragma unroll
+        for (uint32_t sh = 0; sh < 32; sh += 8) {
+            const uint32_t y = (v[c] >> sh) & 0xffu;
+            x = x < y ? x : y;
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t z = uint32_t(__shfl_xor(int(x), o));
+        x = x < z ? x : z;
+    }
+    return x;
+}
+constexpr uint32_t kSegFloorHead = 4;  // 1 KiB pieces of a key read before the rest
+// One wave per hinted window (windows dealt to the waves interleaved, w mod
+// waves: the hot windows are neighbours in slot order), a key's 16 KiB as 16
+// loads of 16 B per lane: 4 in flight, then 12.  The table was zeroed before.
+// (The reduction of a piece to one byte is plain shifts: the 4-byte vector
+// form of it compiled to loads of each piece's first word only.)
+constexpr uint32_t kSegFT = 256;
+__global__ void __launch_bounds__(kSegFT) k_seg_floor(const uint8_t *regs, uint32_t nslots, const SegArgs S) {
+    __shared__ uint32_t nfl;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t nwaves = gridDim.x * (kSegFT / 64), gw = blockIdx.x * (kSegFT / 64) + (tid >> 6);
+    if (tid == 0) nfl = 0;
+    __syncthreads();
+    uint8_t *hot = S.hot + kSegHotHdr;
+    uint32_t mine = 0;
+    if (seg_hot_valid(S)) {
+        // 64 of the wave's windows at a time: lane l holds the hint of window w0 + l * nwaves
+        for (uint32_t w0 = gw; w0 < S.nwin; w0 += nwaves * 64) {
+            const uint32_t wl = w0 + lane * nwaves;
+            const uint32_t hv = wl < S.nwin ? hot[wl] : 0u;
+            if (hv) hot[wl] = uint8_t((hv < kSegHotAge ? hv : kSegHotAge) - 1);
+            for (uint64_t m = __ballot(hv != 0); m; m &= m - 1) {
+                const uint32_t w = w0 + uint32_t(__builtin_ctzll(m)) * nwaves;
+                mine++;
+                for (uint32_t k = 0; k < (1u << S.klog); k++) {
+                    const uint32_t slot = (w << S.klog) | k;
+                    if (slot >= nslots) break;
+                    const part_u32x4 *p = reinterpret_cast<const part_u32x4 *>(regs + (size_t(slot) << kHllP));
+                    // the first quarter alone first: a key not yet saturated
+                    // (floor 0, the table's value already) mostly shows a zero there
+                    part_u32x4 v = p[lane];
+#pragma unroll
+                    for (uint32_t i = 1; i < kSegFloorHead; i++) v = seg_min16(v, p[i * 64 + lane]);
+                    if (seg_wave_min8(v) == 0) continue;
+#pragma unroll
+                    for (uint32_t i = kSegFloorHead; i < (kHllRegs / 16) / 64; i++) v = seg_min16(v, p[i * 64 + lane]);
+                    const uint32_t x = seg_wave_min8(v);
+                    if (lane == 0) S.floor[seg_floor_at(S, w, k)] = uint8_t(x);
+                }
+            }
+        }
+    }
+    if (lane == 0 && mine) atomicAdd(&nfl, mine);
+    __syncthreads();
+    if (tid == 0 && nfl) atomicAdd(S.fstat, (unsigned long long)nfl);
+}
+
 // D: one block per chunk of the sub-batch (grid-stride, in bucket order), its
 // slot fixed or from ctab, its records read whole (16-B loads) and
 // counting-sorted by window within the bucket (o2 / r2 row q = the bucket's
@@ -339,7 +453,12 @@ __global__ void __launch_bounds__(T, SegDA<T>::WPE) k_seg_da(const SegArgs S) {
     __shared__ uint32_t c2[kSegMaxWpb + 1];
     __shared__ __attribute__((aligned(16))) uint32_t sb[kSegChunk];
     __shared__ uint32_t ws[T / 64];
+    __shared__ __attribute__((aligned(16))) uint8_t fls[kSegMaxWpb * 8];  // the bucket's floors by slot-in-bucket
+    __shared__ uint32_t nst[2];
     const uint32_t tid = threadIdx.x, wpb = 1u << S.wlog;
+    const bool ff = S.floor != nullptr;
+    uint32_t nsaw = 0, ndrop = 0;  // this thread's records seen / dropped (the floor statistics)
+    if (tid < 2) nst[tid] = 0;
     const uint32_t *fl = S.fill + seg_fill_at(S, 0);
     uint32_t t = 0;
     if (tid < S.nb1) {
@@ -392,14 +511,31 @@ __global__ void __launch_bounds__(T, SegDA<T>::WPE) k_seg_da(const SegArgs S) {
             rec[4 * k + 3] = v.w;
         }
         for (uint32_t j = tid; j <= wpb; j += T) c2[j] = 0;
+        // the bucket's floors (2^s1 <= 4096 bytes, contiguous in the table)
+        if (ff) {
+            const uint8_t *fb = S.floor + (size_t(h) << S.s1);
+            if (S.s1 >= 4) {
+                if (tid < (1u << (S.s1 - 4)))
+                    reinterpret_cast<part_u32x4 *>(fls)[tid] = reinterpret_cast<const part_u32x4 *>(fb)[tid];
+            } else if (tid < (1u << S.s1)) {
+                fls[tid] = fb[tid];
+            }
+        }
         lds_barrier();
         uint32_t pos[R];
 #pragma unroll
         for (uint32_t j = 0; j < R; j++) {
             pos[j] = 0xffffffffu;
             if ((j / 4 * T + tid) * 4 + j % 4 < n && (rec[j] & 63u) != 0) {  // (rank 0: a C1 pad)
-                const uint32_t w2 = (rec[j] >> (kSegRecShift + S.klog)) & (wpb - 1);
-                pos[j] = (w2 << 16) | atomicAdd(&c2[w2], 1u);
+                // a record at or under its key's floor raises nothing: dropped
+                const uint32_t f = ff ? fls[rec[j] >> kSegRecShift] : 0u;
+                nsaw++;
+                if ((rec[j] & 63u) > f) {
+                    const uint32_t w2 = (rec[j] >> (kSegRecShift + S.klog)) & (wpb - 1);
+                    pos[j] = (w2 << 16) | atomicAdd(&c2[w2], 1u);
+                } else {
+                    ndrop++;
+                }
             }
         }
         lds_barrier();
@@ -418,9 +554,16 @@ __global__ void __launch_bounds__(T, SegDA<T>::WPE) k_seg_da(const SegArgs S) {
         part_u32x4 *dst = reinterpret_cast<part_u32x4 *>(r2 + size_t(q) * kSegChunk);
         const part_u32x4 *src = reinterpret_cast<const part_u32x4 *>(sb);
         for (uint32_t j = tid; j * 4 < total; j += T) nt2_st<4>(dst + j, src[j]);
-        // (the next chunk rewrites c2 before its first barrier: the readers
-        // of this chunk's c2 passed the barrier before the copy-out; sb is
-        // rewritten only after two more barriers)
+        // (the next chunk rewrites c2 and fls before its first barrier: the
+        // readers of this chunk's passed the barrier before the copy-out; sb
+        // is rewritten only after two more barriers)
+    }
+    // the floor statistics: one add per counter, block and launch
+    if (ff) {
+        if (nsaw) atomicAdd(&nst[0], nsaw);
+        if (ndrop) atomicAdd(&nst[1], ndrop);
+        __syncthreads();
+        if (tid < 2 && nst[tid]) atomicAdd(S.fstat + 1 + tid, (unsigned long long)nst[tid]);
     }
 }
 
@@ -513,6 +656,8 @@ __global__ void __launch_bounds__(SegE<KLOG>::T, SegE<KLOG>::WPS) k_seg_e(const 
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t nb1m = S.nb1 - 1;  // buckets: a power of two, window W in bucket W & nb1m
     const uint32_t nitems = QUEUE ? S.q[0] : S.nwin;
+    // E1 keeps the hint map (a map of another plan counts as all zero and is rewritten whole)
+    const bool hinting = !QUEUE && S.hot != nullptr, hot_ok = hinting && seg_hot_valid(S);
     const __amdgpu_buffer_rsrc_t rr2 = part_rsrc(S.r2, S.nsub * S.maxch * kSegChunk * 4);
     // Items (E1: windows, E2: queued slices) go round robin over the blocks.
     // Each item's layout -- its bucket's chunk counts per sub-batch (spre:
@@ -530,6 +675,7 @@ __global__ void __launch_bounds__(SegE<KLOG>::T, SegE<KLOG>::WPS) k_seg_e(const 
     // rarely exceed EP; more are counted and staged in batches.)
     uint32_t cq = 0, cc = 0;                // P1: this thread's sub-batch column
     uint32_t pbase = 0, plen = 0, pnp = 0;  // P2: this thread's run, the item's runs
+    uint32_t hint_n = 0, floor_n = 0;       // P1 (E1, thread 0): the item's hint byte, its keys' highest floor
     auto item = [&](uint32_t it, uint32_t &wi, uint32_t &sl, uint32_t &copy) {
         wi = it;
         sl = 0;
@@ -546,6 +692,14 @@ __global__ void __launch_bounds__(SegE<KLOG>::T, SegE<KLOG>::WPS) k_seg_e(const 
         if (tid < S.nsub) {
             cq = S.cb[size_t(tid) * (S.nb1 + 1) + h];
             cc = S.cb[size_t(tid) * (S.nb1 + 1) + h + 1];
+        }
+        if (hinting && tid == 0) {
+            hint_n = hot_ok ? S.hot[kSegHotHdr + wi] : 0u;
+            floor_n = 0;
+            for (uint32_t k = 0; k < KW && (wi << KLOG) + k < A.nslots; k++) {
+                const uint32_t fk = S.floor[seg_floor_at(S, wi, k)];
+                floor_n = fk > floor_n ? fk : floor_n;
+            }
         }
     };
     // the window's registers into `win` by LDS-DMA (1 KiB per wave
@@ -599,6 +753,7 @@ __global__ void __launch_bounds__(SegE<KLOG>::T, SegE<KLOG>::WPS) k_seg_e(const 
         const uint32_t wi = wi_n, sl = sl_n;
         uint32_t copy = copy_n;
         const uint32_t np = pnp;
+        const uint32_t hv = hint_n, fw = floor_n;
         const uint32_t stamp = QUEUE ? S.nwin + it : wi;
         (void)stamp;
         SEG_STAMP(stamp, 0, 0);
@@ -643,6 +798,14 @@ __global__ void __launch_bounds__(SegE<KLOG>::T, SegE<KLOG>::WPS) k_seg_e(const 
             copy = hdr[0];
         }
         const bool cut = copy != 0xffffffffu;
+        if (hinting && tid == 0) {
+            uint32_t nv = hv;
+            if (nrec) {  // (no record kept: not a visit, the hint ages)
+                const uint64_t est = uint64_t(nrec) << (fw < 31 ? fw : 31), thr = uint64_t(S.hot_min) * nk;
+                nv = cut || est >= thr ? kSegHotAge : (2 * est < thr ? 0u : (hv ? kSegHotAge : 0u));
+            }
+            if (nv != hv || !hot_ok) S.hot[kSegHotHdr + wi] = uint8_t(nv);
+        }
         const uint32_t lo = cut ? sl * SLICE : 0;
         const uint32_t hi = cut ? (nrec - lo < SLICE ? nrec : lo + SLICE) : nrec;
         const bool dense = nrec > 0 && (cut || nrec >= S.dense_min);
@@ -773,6 +936,14 @@ template <int KLOG>
 __global__ void __launch_bounds__(1024) k_seg_m(const PartArgs A, const SegArgs S) {
     constexpr uint32_t KW = 1u << KLOG, WB = KW << kHllP;
     const uint32_t nm = S.q[2];
+    // (E1 has written every window's hint by now: the map belongs to this plan)
+    if (S.hot != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
+        uint32_t *h = reinterpret_cast<uint32_t *>(S.hot);
+        h[0] = S.nwin;
+        h[1] = S.klog;
+        h[2] = S.b1;
+        h[3] = kSegHotMagic;
+    }
     for (uint32_t m = blockIdx.x; m < nm; m += gridDim.x) {
         const uint4 e = S.mlist[m];
         const uint32_t slot0 = e.x << KLOG;
@@ -833,6 +1004,17 @@ hipError_t seg_scratch(const SegPlan &P, uint32_t sub, uint64_t n, Scratch *scr,
     if (e == hipSuccess) S->qitems = (uint4 *)scratch_get(scr, kScrSegQitems, size_t(ccap) * 16, &e);
     if (e == hipSuccess) S->mlist = (uint4 *)scratch_get(scr, kScrSegMlist, size_t(ccap) * 16, &e);
     if (e == hipSuccess) S->copies = (uint8_t *)scratch_get(scr, kScrSegCopies, size_t(ccap) * wb, &e);
+    // the per-key floors: the group's table, the hint map (kept from call to
+    // call: zeroed when allocated) and the statistics
+    S->floor = nullptr;
+    S->hot = nullptr;
+    S->fstat = nullptr;
+    S->hot_min = P.hot_min;
+    if (P.floor) {
+        if (e == hipSuccess) S->floor = (uint8_t *)scratch_get(scr, kScrSegFloor, size_t(P.nb1) << P.s1, &e);
+        if (e == hipSuccess) S->hot = (uint8_t *)scratch_get_zeroed(scr, kScrSegHot, kSegHotHdr + size_t(P.nwin), &e);
+        if (e == hipSuccess) S->fstat = (unsigned long long *)scratch_get_zeroed(scr, kScrSegFstat, 3 * 8, &e);
+    }
     S->ccap = ccap;
     S->nb1 = P.nb1;
     S->s1 = P.s1;
@@ -858,7 +1040,11 @@ hipError_t launch_seg_sub(const PartArgs &A, SegArgs &S, const SegPlan &P, uint3
         // stopped between C1 and D)
         hipError_t e = hipMemsetAsync(S.fill, 0, size_t(P.nsub) * (P.nb1 + 1) * kSegFillStride * 4, st);
         if (e == hipSuccess) e = hipMemsetAsync(S.ctab, 0, size_t(P.nb1) * S.kmaxc * 4, st);
+        // the group's floors, from the slab as it stands now
+        if (e == hipSuccess && S.floor) e = hipMemsetAsync(S.floor, 0, size_t(P.nb1) << P.s1, st);
         if (e != hipSuccess) return e;
+        if (S.floor)
+            hipLaunchKernelGGL(k_seg_floor, dim3(unsigned(cus) * 4), dim3(kSegFT), 0, st, A.regs, A.nslots, S);
     }
     hipLaunchKernelGGL(k_seg_c1<kSegC1T>, dim3(std::min(S.nruns, unsigned(cus) * SegC1<kSegC1T>::BPC)), dim3(kSegC1T),
                        0, st, A, S);

@@ -17,6 +17,7 @@ constexpr uint32_t kSegRun = 8192;    // swipes per C1 run (sketch_part.h: kSegR
 // the segmented PFADD's geometry for one batch (seg_plan)
 struct SegPlan {
     uint32_t s1, b1, wlog, klog, nb1, nwin, maxch, nsub, dense_min;
+    uint32_t floor, hot_min;  // the per-key floors: on, and E's hint threshold (arrivals per key and group)
 };
 
 // Records C1 can reserve in one sub-batch of at most `sub` swipes, pads
@@ -95,6 +96,8 @@ inline bool seg_plan(uint32_t nslots, uint64_t n, uint32_t sub, const SegOpts &s
     P->nsub = uint32_t(std::min<uint64_t>(std::min<uint64_t>(ns, kmax), 64));
     const uint64_t dm = uint64_t(so.dense_min_x100) * ((uint64_t(1) << klog) * (kHllRegs / 128)) / 100;
     P->dense_min = dm < 1 ? 1u : (dm > 0xffffffffu ? 0xffffffffu : uint32_t(dm));
+    P->floor = so.floor != 0;
+    P->hot_min = so.hot_min;
     return true;
 }
 

@@ -390,6 +390,13 @@ class SketchEngine:
         self.ctx.call("ske_pass_times", ms, cnt, 1 if reset else 0)
         return [(ms[i], cnt[i]) for i in range(PASS_KINDS)]
 
+    def seg_floor_stats(self) -> tuple[int, int, int]:
+        """(windows floored, records the level-2 sort saw, records it dropped)
+        of the segmented PFADD since the last read; waits for the stream."""
+        out = (C.c_uint64 * 3)()
+        self.ctx.call("ske_seg_floor_stats", out)
+        return int(out[0]), int(out[1]), int(out[2])
+
     def set_stream(self, stream_ptr: int | None):
         self.ctx.call("ske_set_stream", C.c_void_p(stream_ptr) if stream_ptr else None)
 
