@@ -156,6 +156,10 @@ class BloomMixin:
                 raise ResponseError("ERR item exists")
             if h["options"] & formats.BLOOM_OPT_FORCE64 == 0 or not h["links"]:
                 raise ResponseError("ERR received bad data")
+            # bloom_check_add64 probes mod 2^n2 when n2 != 0; the device always
+            # probes mod bits, so only a link whose bits are that power of two loads
+            if any(L["n2"] and (L["n2"] > 63 or L["bits"] != 1 << L["n2"]) for L in h["links"]):
+                raise ResponseError("ERR received bad data")
             arr = (BfLink * len(h["links"]))()
             for i, L in enumerate(h["links"]):
                 arr[i].entries, arr[i].bytes, arr[i].bits = L["entries"], L["bytes"], L["bits"]

@@ -458,6 +458,26 @@ def test_facade_transcript(pkg):
             assert gs == ws, f"{g['case']}: {gs['step']}"
 
 
+def test_bf_loadchunk_header_n2(pkg):
+    """A link's n2 (last byte of its header record) makes RedisBloom probe mod
+    2^n2; the device probes mod bits.  A header whose n2 is not log2(bits) is
+    "ERR received bad data": no native call, no key left behind.  n2 == log2(bits)
+    (here 1024 bits, n2 = 10) loads as ever."""
+    def hdr(n2):
+        return pkg.formats.bf_dump_header(3, [_link()], 2, False)[:-1] + bytes([n2])
+
+    for bad in (9, 11, 64, 255):
+        r = _Recorder(pkg)
+        e = r.do("bad n2", r.cl.bf_loadchunk, "k", 1, hdr(bad))
+        assert type(e).__name__ == "ResponseError" and str(e) == "ERR received bad data"
+        assert r.steps[-1]["calls"] == []
+        assert r.ex("TYPE", "k") == "none" and r.cl.keys.fid == {}
+    r = _Recorder(pkg)
+    assert r.do("n2 = log2(bits)", r.cl.bf_loadchunk, "k", 1, hdr(10)) is True
+    assert [c[0] for c in r.steps[-1]["calls"]] == ["ske_bf_load_header"]
+    assert r.ex("TYPE", "k") == "MBbloom--"
+
+
 if __name__ == "__main__":
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
