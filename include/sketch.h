@@ -348,6 +348,22 @@ int ske_cms_merge(ske_ctx *ctx, uint32_t dst, const uint32_t *srcs, const int64_
  * overwrites cells and count (ncells must equal width * depth) */
 int ske_cms_export(ske_ctx *ctx, uint32_t cid, uint32_t *out, uint64_t cap_cells);
 int ske_cms_import(ske_ctx *ctx, uint32_t cid, const uint32_t *in, uint64_t ncells, uint64_t count);
+/* The table's device pointer (row-major cells, *ncells = width * depth), as
+ * ske_hll_slab gives the slab's: the source of an all-gather across contexts.
+ * The allocation is padded to the next 16 bytes, so ((*ncells + 3) & ~3) cells
+ * are readable.  The count is not part of it (ske_cms_info). */
+int ske_cms_table_dev(ske_ctx *ctx, uint32_t cid, void **cells_dev, uint64_t *ncells);
+/* dst = the saturating sum of ntables caller-owned device tables (several
+ * contexts' tables, gathered): table k is the cells at tables_dev + k *
+ * stride_cells, stride_cells a multiple of 4 and at least dst's width * depth,
+ * tables_dev 16-byte aligned (else SKE_EINVAL); counts is a HOST array of
+ * ntables counts.  dst is overwritten: cell = min(sum over the tables,
+ * 2^32 - 1), count = sum of counts.  Saturation, not ske_cms_merge's overflow
+ * error: the bulk add saturates, and this is the table one context would have
+ * built from all the increments.  A count sum beyond 2^64 - 1: SKE_ECMSOVERFLOW
+ * before dst is written.  1 <= ntables <= SKE_CMS_MAX_MERGE.  Enqueue only. */
+int ske_cms_sum_dev(ske_ctx *ctx, uint32_t dst_cid, const uint32_t *tables_dev, uint64_t stride_cells,
+                    uint32_t ntables, const uint64_t *counts);
 
 /* ---- heavy hitters beside a Count-Min Sketch table ----
  * A set of distinct ids (at most SKE_HH_ID_BYTES bytes each) in 2^capacity_log2
@@ -444,6 +460,23 @@ int ske_hh_stats(ske_ctx *ctx, uint32_t hid, uint32_t cid, uint32_t threshold, s
  * touched. */
 int ske_hh_select(ske_ctx *ctx, uint32_t hid, uint32_t cid, uint32_t threshold, const uint64_t *ranks,
                   uint32_t nranks, uint32_t *out_est, uint64_t *n_out);
+/* The union of sets across contexts.  Export: every member, unordered, into
+ * caller-owned device arrays (ids_dev 8-byte aligned, cap x SKE_HH_ID_BYTES
+ * zero-padded bytes; lens_dev cap entries); no table, no estimates.  *n_out =
+ * the members, *overflow_out = the sticky overflow word; more members than
+ * cap: SKE_EHHSPACE with both still written (cap >= used always suffices).
+ * Returns when done; SKE_EBUSY while a capture is recording.
+ * Merge: every entry of such arrays joins the set, with no threshold; the same
+ * id any number of times lands once.  The bytes behind an entry's length are
+ * masked, not trusted; an entry with a length over SKE_HH_ID_BYTES is skipped
+ * and sets the overflow word, as ske_hh_track_packed_async does; the load limit
+ * and the probe bound refuse as a track's do.  foreign_overflow != 0 (the
+ * source's overflow word) sets the overflow word: a source that refused an id
+ * makes the union incomplete.  n < 2^32 - 1.  Enqueue only. */
+int ske_hh_export_dev(ske_ctx *ctx, uint32_t hid, uint8_t *ids_dev, uint32_t *lens_dev, uint64_t cap,
+                      uint64_t *n_out, uint32_t *overflow_out);
+int ske_hh_merge_dev(ske_ctx *ctx, uint32_t hid, const uint8_t *ids_dev, const uint32_t *lens_dev, uint64_t n,
+                     uint32_t foreign_overflow);
 
 /* ---- time profile: weekday x hour counters of the swipes' times ----
  * SKE_TP_BINS u64 counters on the device, addressed by a caller-chosen tid <
@@ -570,6 +603,25 @@ int ske_tally_top(ske_ctx *ctx, uint32_t tid, uint32_t k, int by, uint8_t *head_
  * events[i] or non-zero padding: SKE_EINVAL; nothing is added then. */
 int ske_tally_import(ske_ctx *ctx, uint32_t tid, const uint8_t *keys, const uint32_t *lens, const uint64_t *events,
                      const uint64_t *valid, uint64_t n);
+/* The sum of tallies across contexts.  Export: every entry, unordered, in the
+ * listing's layout, into caller-owned device arrays (keys_dev 8-byte aligned,
+ * cap x SKE_TALLY_KEY_BYTES zero-padded bytes; the others cap entries).
+ * *n_out = the entries; more than cap: SKE_ETALLYSPACE, *n_out still written.
+ * Returns when done; SKE_EBUSY while a capture is recording.
+ * Merge: insert-or-add of n such entries, and the head receives the source's
+ * refused counts: taken grows by the events and by dropped_events,
+ * dropped_events / dropped_valid by theirs, foreign_overflow != 0 sets the
+ * overflow word.  So sum of events + dropped_events == taken still holds after
+ * the merge, and the same for valid.  Precondition: valid[i] <= events[i] --
+ * the arrays are another tally's export, not outside input, and are not
+ * checked.  A length over SKE_TALLY_KEY_BYTES goes the too-long way: dropped,
+ * overflow set.  A refusal at this tally's load limit or probe bound moves the
+ * entry's counts to dropped_*.  n < 2^32 - 1.  Enqueue only. */
+int ske_tally_export_dev(ske_ctx *ctx, uint32_t tid, uint8_t *keys_dev, uint32_t *lens_dev, uint64_t *events_dev,
+                         uint64_t *valid_dev, uint64_t cap, uint64_t *n_out);
+int ske_tally_merge_dev(ske_ctx *ctx, uint32_t tid, const uint8_t *keys_dev, const uint32_t *lens_dev,
+                        const uint64_t *events_dev, const uint64_t *valid_dev, uint64_t n, uint64_t dropped_events,
+                        uint64_t dropped_valid, uint32_t foreign_overflow);
 
 /* ---- the fused hot path (K1) ----
  * For every swipe i: v = BF.EXISTS fid id_i; if v: PFADD slot_i id_i.

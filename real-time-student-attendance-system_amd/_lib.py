@@ -197,6 +197,8 @@ SIGNATURES = {
     "ske_cms_merge": (C.c_int, [_CTX, C.c_uint32, _u32p, _vp, C.c_uint32]),
     "ske_cms_export": (C.c_int, [_CTX, C.c_uint32, _u32p, C.c_uint64]),
     "ske_cms_import": (C.c_int, [_CTX, C.c_uint32, _u32p, C.c_uint64, C.c_uint64]),
+    "ske_cms_table_dev": (C.c_int, [_CTX, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "ske_cms_sum_dev": (C.c_int, [_CTX, C.c_uint32, _u32p, C.c_uint64, C.c_uint32, _u64p]),
     "ske_hh_init": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),
     "ske_hh_free": (C.c_int, [_CTX, C.c_uint32]),
     "ske_hh_reset": (C.c_int, [_CTX, C.c_uint32]),
@@ -211,6 +213,9 @@ SIGNATURES = {
     "ske_hh_stats": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(HhStats)]),
     "ske_hh_select": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, C.c_uint32, _u32p,
                                 C.POINTER(C.c_uint64)]),
+    "ske_hh_export_dev": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, C.c_uint64, C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint32)]),
+    "ske_hh_merge_dev": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, C.c_uint64, C.c_uint32]),
     "ske_tp_init": (C.c_int, [_CTX, C.c_uint32]),
     "ske_tp_free": (C.c_int, [_CTX, C.c_uint32]),
     "ske_tp_reset": (C.c_int, [_CTX, C.c_uint32]),
@@ -231,6 +236,10 @@ SIGNATURES = {
     "ske_tally_top": (C.c_int, [_CTX, C.c_uint32, C.c_uint32, C.c_int, _u8p, _u32p, _u64p, _u64p, _u8p, _u32p,
                                 _u64p, _u64p, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "ske_tally_import": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, _u64p, _u64p, C.c_uint64]),
+    "ske_tally_export_dev": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, _u64p, _u64p, C.c_uint64,
+                                       C.POINTER(C.c_uint64)]),
+    "ske_tally_merge_dev": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, _u64p, _u64p, C.c_uint64, C.c_uint64,
+                                      C.c_uint64, C.c_uint32]),
     "ske_swipes": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p, C.c_int]),
     "ske_swipes_async": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p]),
     "ske_swipes_fixed": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, C.c_uint32, C.c_uint64, _u8p,
@@ -306,6 +315,18 @@ def load() -> C.CDLL:
 def ptr(a):
     """A numpy array (or None) as the void pointer argument of a call."""
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def devptr(x):
+    """A device array as the void pointer argument of a call: a torch tensor
+    (``data_ptr()``), an ``engine.DeviceBuffer`` (``ptr``), an address, or None."""
+    if x is None:
+        return None
+    if hasattr(x, "data_ptr"):
+        return C.c_void_p(x.data_ptr())
+    if hasattr(x, "ptr"):
+        return C.c_void_p(x.ptr)
+    return C.c_void_p(int(x))
 
 
 def strerror(code: int) -> str:

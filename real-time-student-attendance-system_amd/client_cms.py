@@ -165,6 +165,27 @@ class CmsMixin:
         self.ctx.call("ske_cms_export", t, _ptr(out), out.size)
         return out, i["count"]
 
+    def cms_table_dev(self, key) -> tuple[int, int]:
+        """``(address, ncells)`` of the table on the device (row-major u32
+        cells; ``(ncells + 3) & ~3`` of them are readable): the source of an
+        all-gather across contexts.  The count is ``cms_info``'s."""
+        p, n = C.c_void_p(), C.c_uint64()
+        self.ctx.call("ske_cms_table_dev", self.cms_cid(key), C.byref(p), C.byref(n))
+        return int(p.value), int(n.value)
+
+    def cms_sum_dev(self, dest, tables, stride_cells: int, counts) -> None:
+        """``dest`` = the saturating sum of ``len(counts)`` tables on the device
+        (a torch tensor, a DeviceBuffer or an address, 16-byte aligned; table k
+        ``stride_cells`` cells behind table k - 1) and of their counts.
+        Enqueue only: the tables stay as they are until the context's stream
+        has run (``ske_sync``)."""
+        cnt = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+        try:
+            self.ctx.call("ske_cms_sum_dev", self.cms_cid(dest), _lib.devptr(tables), int(stride_cells),
+                          int(cnt.size), _ptr(cnt))
+        except SketchLibError as e:
+            raise ResponseError(str(e))
+
     # ---- command handlers (commands.COMMANDS)
     def _cmd_cms_incrby(self, a):
         if len(a) % 2 == 0:

@@ -8,6 +8,7 @@ sets, by name.  ``DEL`` of the bound CMS key and ``FLUSHALL`` free them; while
 no set exists neither makes any further native call."""
 from __future__ import annotations
 
+import ctypes as C
 import math
 
 import numpy as np
@@ -99,6 +100,23 @@ class HhMixin:
         step = _lib.SKE_HH_MAX_RANKS
         parts = [hh_select(self.ctx, hid, cid, threshold, r[i:i + step]) for i in range(0, r.size, step)]
         return np.concatenate(parts) if parts else np.zeros(0, np.uint32)
+
+    def hh_export_dev(self, name, ids, lens, cap: int) -> tuple[int, int]:
+        """Every member, unordered, into device arrays of ``cap`` entries
+        (``ids``: 16 zero-padded bytes each, 8-byte aligned; ``lens``: u32);
+        returns ``(members, the set's overflow word)``.  More members than
+        ``cap`` raises (SKE_EHHSPACE)."""
+        n, ov = C.c_uint64(0), C.c_uint32(0)
+        self.ctx.call("ske_hh_export_dev", self._hh_entry(name)[0], _lib.devptr(ids), _lib.devptr(lens), int(cap),
+                      C.byref(n), C.byref(ov))
+        return int(n.value), int(ov.value)
+
+    def hh_merge_dev(self, name, ids, lens, n: int, foreign_overflow: int = 0) -> None:
+        """The ``n`` entries of another set's export join this one (no
+        threshold); ``foreign_overflow``: the source's overflow word.  Enqueue
+        only: the arrays stay as they are until the context's stream has run."""
+        self.ctx.call("ske_hh_merge_dev", self._hh_entry(name)[0], _lib.devptr(ids), _lib.devptr(lens), int(n),
+                      1 if foreign_overflow else 0)
 
     def hh_quantile(self, name, q: float, threshold: int = 0) -> float:
         """The ``q``-quantile of those estimates as ``np.quantile`` computes it

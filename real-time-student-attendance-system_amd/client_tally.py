@@ -7,6 +7,8 @@ the client keeps its own registry of live tallies, by name.  ``FLUSHALL``
 frees them; while no tally exists it makes no further native call."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 
 from . import _lib
@@ -100,6 +102,26 @@ class TallyMixin:
         if not 1 <= int(k) <= _lib.SKE_TALLY_MAX_TOP:
             raise ValueError(f"k is between 1 and {_lib.SKE_TALLY_MAX_TOP}")
         return tally_top(self.ctx, self.tally_tid(name), k, TALLY_BY[by])
+
+    def tally_export_dev(self, name, keys, lens, events, valid, cap: int) -> int:
+        """Every entry, unordered, into device arrays of ``cap`` entries
+        (``keys``: 32 zero-padded bytes each, 8-byte aligned; ``lens`` u32;
+        ``events`` / ``valid`` u64); returns how many.  More entries than
+        ``cap`` raises (SKE_ETALLYSPACE)."""
+        n = C.c_uint64(0)
+        self.ctx.call("ske_tally_export_dev", self.tally_tid(name), _lib.devptr(keys), _lib.devptr(lens),
+                      _lib.devptr(events), _lib.devptr(valid), int(cap), C.byref(n))
+        return int(n.value)
+
+    def tally_merge_dev(self, name, keys, lens, events, valid, n: int, dropped_events: int = 0,
+                        dropped_valid: int = 0, foreign_overflow: int = 0) -> None:
+        """Insert-or-add of the ``n`` entries of another tally's export; the
+        head takes the source's ``dropped_*`` and overflow (its
+        ``tally_info``).  Enqueue only: the arrays stay as they are until the
+        context's stream has run."""
+        self.ctx.call("ske_tally_merge_dev", self.tally_tid(name), _lib.devptr(keys), _lib.devptr(lens),
+                      _lib.devptr(events), _lib.devptr(valid), int(n), int(dropped_events), int(dropped_valid),
+                      1 if foreign_overflow else 0)
 
     def tally_import(self, name, keys, events, valid) -> None:
         """Insert-or-add of a listing (another tally's, another rank's)."""

@@ -264,4 +264,28 @@ int ske_cms_import(ske_ctx *c, uint32_t cid, const uint32_t *in, uint64_t ncells
     return SKE_OK;
 }
 
+int ske_cms_table_dev(ske_ctx *c, uint32_t cid, void **cells_dev, uint64_t *ncells) {
+    if (!c || !cells_dev || !ncells) return SKE_EINVAL;
+    Cms *T = get_cms(c, cid);
+    if (!T) return SKE_ECMSNOKEY;
+    *cells_dev = T->cells;
+    *ncells = uint64_t(T->width) * T->depth;
+    return SKE_OK;
+}
+
+int ske_cms_sum_dev(ske_ctx *c, uint32_t dst_cid, const uint32_t *tables_dev, uint64_t stride_cells, uint32_t ntables,
+                    const uint64_t *counts) {
+    if (!c || !tables_dev || !counts || ntables == 0 || ntables > SKE_CMS_MAX_MERGE) return SKE_EINVAL;
+    Cms *D = get_cms(c, dst_cid);
+    if (!D) return SKE_ECMSNOKEY;
+    const uint64_t ncells = uint64_t(D->width) * D->depth;
+    if ((stride_cells & 3) || stride_cells < ncells || (reinterpret_cast<uintptr_t>(tables_dev) & 15))
+        return SKE_EINVAL;
+    unsigned long long cnt = 0;
+    for (uint32_t k = 0; k < ntables; k++)
+        if (__builtin_add_overflow(cnt, (unsigned long long)counts[k], &cnt)) return SKE_ECMSOVERFLOW;
+    HIPCHK(c, launch_cms_sum(table_of(*D), tables_dev, stride_cells, ntables, cnt, c->cus, c->st));
+    return SKE_OK;
+}
+
 }  // extern "C"

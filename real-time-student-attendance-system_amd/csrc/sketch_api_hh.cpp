@@ -254,6 +254,45 @@ int ske_hh_list(ske_ctx *c, uint32_t hid, uint32_t cid, uint32_t threshold, uint
     return SKE_OK;
 }
 
+int ske_hh_export_dev(ske_ctx *c, uint32_t hid, uint8_t *ids_dev, uint32_t *lens_dev, uint64_t cap, uint64_t *n_out,
+                      uint32_t *overflow_out) {
+    if (!c || !n_out || !overflow_out) return SKE_EINVAL;
+    Hh *H = get_hh(c, hid);
+    if (!H) return SKE_EHHNOSET;
+    if (c->capturing) {
+        c->last_hip = "ske_hh_export_dev waits for the stream and cannot be recorded";
+        return SKE_EBUSY;
+    }
+    if (cap && (!ids_dev || !lens_dev || (reinterpret_cast<uintptr_t>(ids_dev) & 7))) return SKE_EINVAL;
+    // no more than the capacity can pass
+    const uint64_t slots = uint64_t(1) << H->log2;
+    const uint32_t dcap = uint32_t(cap < slots ? cap : slots);
+    int rc = SKE_OK;
+    unsigned int *cnt = (unsigned int *)stage_buf(c, kStgHhFlag, 16, &rc);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(cnt, 0, 16, c->st));
+    HIPCHK(c, launch_hh_export(set_of(*H), dcap, reinterpret_cast<uint64_t *>(ids_dev), lens_dev, cnt, c->st));
+    unsigned int n = 0, head[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(&n, cnt, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(head, H->base, 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    *n_out = n;
+    *overflow_out = head[1];
+    return n > cap ? SKE_EHHSPACE : SKE_OK;
+}
+
+int ske_hh_merge_dev(ske_ctx *c, uint32_t hid, const uint8_t *ids_dev, const uint32_t *lens_dev, uint64_t n,
+                     uint32_t foreign_overflow) {
+    if (!c) return SKE_EINVAL;
+    Hh *H = get_hh(c, hid);
+    if (!H) return SKE_EHHNOSET;
+    if (n >= 0xffffffffull) return SKE_EINVAL;
+    if (n && (!ids_dev || !lens_dev || (reinterpret_cast<uintptr_t>(ids_dev) & 7))) return SKE_EINVAL;
+    HIPCHK(c, launch_hh_merge(set_of(*H), reinterpret_cast<const uint64_t *>(ids_dev), lens_dev, uint32_t(n),
+                              foreign_overflow, c->cus, c->st));
+    return SKE_OK;
+}
+
 }  // extern "C"
 
 // ske_hh_stats and ske_hh_select: the record zeroed, the whole chain of

@@ -450,4 +450,51 @@ int ske_tally_import(ske_ctx *c, uint32_t tid, const uint8_t *keys, const uint32
     return SKE_OK;
 }
 
+int ske_tally_export_dev(ske_ctx *c, uint32_t tid, uint8_t *keys_dev, uint32_t *lens_dev, uint64_t *events_dev,
+                         uint64_t *valid_dev, uint64_t cap, uint64_t *n_out) {
+    if (!c || !n_out) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Tally *Y = tally_for_sync_call(c, tid, "ske_tally_export_dev", &rc);
+    if (!Y) return rc;
+    if (cap && (!keys_dev || !lens_dev || !events_dev || !valid_dev || (reinterpret_cast<uintptr_t>(keys_dev) & 7)))
+        return SKE_EINVAL;
+    // no more than the capacity can pass
+    const uint64_t slots = uint64_t(1) << Y->log2;
+    const uint32_t dcap = uint32_t(cap < slots ? cap : slots);
+    unsigned int *cnt = (unsigned int *)stage_buf(c, kStgTallyFlag, 16, &rc);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(cnt, 0, 16, c->st));
+    HIPCHK(c, launch_tally_list(tab_of(*Y), 0, dcap, reinterpret_cast<uint64_t *>(keys_dev), lens_dev, events_dev,
+                                valid_dev, cnt, c->st));
+    unsigned int n = 0;
+    HIPCHK(c, hipMemcpyAsync(&n, cnt, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    *n_out = n;
+    return n > cap ? SKE_ETALLYSPACE : SKE_OK;
+}
+
+int ske_tally_merge_dev(ske_ctx *c, uint32_t tid, const uint8_t *keys_dev, const uint32_t *lens_dev,
+                        const uint64_t *events_dev, const uint64_t *valid_dev, uint64_t n, uint64_t dropped_events,
+                        uint64_t dropped_valid, uint32_t foreign_overflow) {
+    if (!c || tid >= SKE_MAX_TALLY) return SKE_EINVAL;
+    Tally *Y = get_tally(c, tid);
+    if (!Y) return SKE_ETALLYNOSET;
+    if (n >= 0xffffffffull) return SKE_EINVAL;
+    if (n && (!keys_dev || !lens_dev || !events_dev || !valid_dev || (reinterpret_cast<uintptr_t>(keys_dev) & 7)))
+        return SKE_EINVAL;
+    if (n) {
+        TallyItems I{};
+        I.kind = 3;
+        I.bytes = keys_dev;
+        I.len = lens_dev;
+        I.ev = events_dev;
+        I.va = valid_dev;
+        I.n = uint32_t(n);
+        const int rc = tally_launch(c, *Y, I);
+        if (rc) return rc;
+    }
+    HIPCHK(c, launch_tally_head_add(tab_of(*Y), dropped_events, dropped_valid, foreign_overflow, c->st));
+    return SKE_OK;
+}
+
 }  // extern "C"

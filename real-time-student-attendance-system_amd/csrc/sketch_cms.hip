@@ -150,6 +150,45 @@ __global__ void __launch_bounds__(kCmsBlock) k_cms_merge(const CmsMergeArgs M) {
     if (!kWrite && bad) atomicOr(M.flag, 1u);
 }
 
+// The saturating sum of caller-owned tables (the ranks' tables after an
+// all-gather): a stream over the cells, 16 bytes a load from every table, the
+// sums in 64 bits (at most 64 tables of 32-bit cells: no overflow), a cell that
+// would pass 2^32 - 1 stays there -- the table one context's bulk adds build.
+// Apart from k_cms_merge: no weights, no check pass, no failure.  Thread c reads
+// every table's cells before it writes dst's, and nobody else touches them, so
+// dst's own cells may be one of the tables.
+__device__ __forceinline__ uint32_t cms_sat32(unsigned long long v) {
+    return v > 0xffffffffull ? 0xffffffffu : uint32_t(v);
+}
+
+__global__ void __launch_bounds__(kCmsBlock) k_cms_sum(uint32_t *dst, unsigned long long *dst_count,
+                                                        const uint32_t *tables, uint64_t stride, uint32_t ntables,
+                                                        uint32_t ncells, unsigned long long count) {
+    const uint32_t nvec = ncells >> 2;
+    const uint32_t step = gridDim.x * kCmsBlock;
+    for (uint32_t v = blockIdx.x * kCmsBlock + threadIdx.x; v < nvec; v += step) {
+        unsigned long long a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+        for (uint32_t k = 0; k < ntables; k++) {
+            const uint4 x = reinterpret_cast<const uint4 *>(tables + k * stride)[v];
+            a0 += x.x;
+            a1 += x.y;
+            a2 += x.z;
+            a3 += x.w;
+        }
+        reinterpret_cast<uint4 *>(dst)[v] = make_uint4(cms_sat32(a0), cms_sat32(a1), cms_sat32(a2), cms_sat32(a3));
+    }
+    if (blockIdx.x == 0) {
+        // the tail: ncells & 3 cells behind the last whole vector
+        const uint32_t c = (nvec << 2) + threadIdx.x;
+        if (threadIdx.x < 4 && c < ncells) {
+            unsigned long long a = 0;
+            for (uint32_t k = 0; k < ntables; k++) a += tables[k * stride + c];
+            dst[c] = cms_sat32(a);
+        }
+        if (threadIdx.x == 0) *dst_count = count;
+    }
+}
+
 unsigned grid_for(uint64_t n, unsigned block, unsigned cap) {
     const uint64_t want = (n + block - 1) / block;
     return unsigned(want < cap ? (want ? want : 1) : cap);
@@ -197,6 +236,14 @@ hipError_t launch_cms_merge(const CmsMergeArgs &M, bool write, int cus, hipStrea
         hipLaunchKernelGGL(k_cms_merge<true>, dim3(grid), dim3(kCmsBlock), 0, st, M);
     else
         hipLaunchKernelGGL(k_cms_merge<false>, dim3(grid), dim3(kCmsBlock), 0, st, M);
+    return hipGetLastError();
+}
+
+hipError_t launch_cms_sum(const CmsTable &D, const uint32_t *tables, uint64_t stride, uint32_t ntables,
+                          unsigned long long count, int cus, hipStream_t st) {
+    const unsigned grid = grid_for(D.ncells / 4, kCmsBlock, unsigned(cus) * 8);
+    hipLaunchKernelGGL(k_cms_sum, dim3(grid), dim3(kCmsBlock), 0, st, D.cells, D.count, tables, stride, ntables,
+                       D.ncells, count);
     return hipGetLastError();
 }
 

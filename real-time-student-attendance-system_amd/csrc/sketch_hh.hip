@@ -9,6 +9,8 @@
 //   k_hh_list   one thread per slot: an occupied slot recomputes its estimate
 //               from the stored words; those that pass are appended to the
 //               output through one counter add per wavefront.
+//   k_hh_export every member into caller-owned device arrays (no table), and
+//   k_hh_merge  such arrays into a set: the union of sets across contexts.
 //
 // The set is an insert-only open-addressing table.  A slot is a claim word (the
 // id's 64-bit digest, 0 = empty), 16 id bytes as two words, and the length.
@@ -139,6 +141,51 @@ __global__ void __launch_bounds__(kHhBlock) k_hh_list(const CmsTable T, const Hh
     out_est[at] = est;
 }
 
+// k_hh_list without a table: every member, unordered (the whole set on its way
+// to another context).  The same grid, the same append.
+__global__ void __launch_bounds__(kHhBlock) k_hh_export(const HhSet S, uint32_t cap, uint64_t *out_ids,
+                                                         uint32_t *out_len, unsigned int *out_n) {
+    const uint32_t slot = blockIdx.x * kHhBlock + threadIdx.x;
+    const bool pass = S.claim[slot] != 0;
+    const unsigned long long votes = __ballot(pass);
+    if (votes == 0) return;
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(out_n, uint32_t(__popcll(votes)));
+    base = __shfl(base, 0, 64);
+    if (!pass) return;
+    const uint32_t at = base + uint32_t(__popcll(votes & ((1ull << lane) - 1)));
+    if (at >= cap) return;
+    out_ids[2 * uint64_t(at)] = S.ids[2 * uint64_t(slot)];
+    out_ids[2 * uint64_t(at) + 1] = S.ids[2 * uint64_t(slot) + 1];
+    out_len[at] = S.len[slot];
+}
+
+// Another set's export joins S: hh_insert per entry, no threshold and no table.
+// The bytes behind an entry's length are masked, not trusted -- they take part
+// in the digest.  A length over 16 is skipped and is a refused insert.
+__global__ void __launch_bounds__(kHhBlock) k_hh_merge(const HhSet S, const uint64_t *ids, const uint32_t *len,
+                                                        uint32_t n, uint32_t foreign_overflow) {
+    if (foreign_overflow && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(S.overflow, 1u);
+    const uint64_t stride = uint64_t(gridDim.x) * kHhBlock;
+    for (uint64_t i = uint64_t(blockIdx.x) * kHhBlock + threadIdx.x; i < n; i += stride) {
+        Item it{};
+        it.len = len[i];
+        if (it.len > 16) {
+            atomicOr(S.overflow, 1u);
+            continue;
+        }
+        it.w0 = ids[2 * i];
+        it.w1 = ids[2 * i + 1];
+        if (it.len < 8) it.w0 = it.len ? it.w0 & ((uint64_t(1) << (it.len * 8)) - 1) : 0;
+        if (it.len <= 8)
+            it.w1 = 0;
+        else if (it.len < 16)
+            it.w1 &= (uint64_t(1) << ((it.len - 8) * 8)) - 1;
+        hh_insert(S, it);
+    }
+}
+
 }  // namespace
 
 hipError_t hh_setup() {
@@ -170,6 +217,24 @@ hipError_t launch_hh_list(const CmsTable &T, const HhSet &S, uint32_t threshold,
     if (slots % kHhBlock) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_hh_list, dim3(slots / kHhBlock), dim3(kHhBlock), 0, st, T, S, threshold, cap, out_ids,
                        out_len, out_est, out_n);
+    return hipGetLastError();
+}
+
+hipError_t launch_hh_export(const HhSet &S, uint32_t cap, uint64_t *out_ids, uint32_t *out_len, unsigned int *out_n,
+                            hipStream_t st) {
+    const uint32_t slots = S.mask + 1;
+    if (slots % kHhBlock) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_hh_export, dim3(slots / kHhBlock), dim3(kHhBlock), 0, st, S, cap, out_ids, out_len, out_n);
+    return hipGetLastError();
+}
+
+hipError_t launch_hh_merge(const HhSet &S, const uint64_t *ids, const uint32_t *len, uint32_t n,
+                           uint32_t foreign_overflow, int cus, hipStream_t st) {
+    if (n == 0 && !foreign_overflow) return hipSuccess;
+    const uint64_t want = (uint64_t(n) + kHhBlock - 1) / kHhBlock;
+    const uint64_t most = uint64_t(cus) * 8;
+    const unsigned grid = unsigned(want < most ? (want ? want : 1) : most);
+    hipLaunchKernelGGL(k_hh_merge, dim3(grid), dim3(kHhBlock), 0, st, S, ids, len, n, foreign_overflow);
     return hipGetLastError();
 }
 

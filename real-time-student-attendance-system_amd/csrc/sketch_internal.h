@@ -233,6 +233,10 @@ hipError_t launch_cms_seq(const CmsTable &T, const CmsItems &I, uint32_t *reply,
 hipError_t launch_cms_query(const CmsTable &T, const CmsItems &I, uint32_t *out, int cus, hipStream_t st);
 // write == false: only the range check into M.flag; true: dst = the weighted sums
 hipError_t launch_cms_merge(const CmsMergeArgs &M, bool write, int cus, hipStream_t st);
+// D's cells = min(sum over ntables tables, 2^32 - 1), table k at tables + k * stride (cells; stride a
+// multiple of 4 and >= D.ncells, tables 16-byte aligned), *D.count = count
+hipError_t launch_cms_sum(const CmsTable &D, const uint32_t *tables, uint64_t stride, uint32_t ntables,
+                          unsigned long long count, int cus, hipStream_t st);
 
 // sketch_hh.hip -- heavy-hitter sets beside a Count-Min Sketch table: ids whose
 // estimate reached a threshold, in an insert-only open-addressing table
@@ -259,6 +263,13 @@ hipError_t launch_hh_track(const CmsTable &T, const CmsItems &I, const HhSet &S,
 // out_ids[2j..], out_len[j], out_est[j]; *out_n (zeroed by the caller) counts all that pass
 hipError_t launch_hh_list(const CmsTable &T, const HhSet &S, uint32_t threshold, uint32_t cap, uint64_t *out_ids,
                           uint32_t *out_len, uint32_t *out_est, unsigned int *out_n, hipStream_t st);
+// every member, unordered, no table: entry j < min(*out_n, cap) in out_ids[2j..], out_len[j]
+hipError_t launch_hh_export(const HhSet &S, uint32_t cap, uint64_t *out_ids, uint32_t *out_len, unsigned int *out_n,
+                            hipStream_t st);
+// every entry (16 padded id bytes at ids + 2i, len[i]) joins S, no threshold; len[i] > 16 is skipped
+// and sets S's overflow word, as foreign_overflow != 0 does
+hipError_t launch_hh_merge(const HhSet &S, const uint64_t *ids, const uint32_t *len, uint32_t n,
+                           uint32_t foreign_overflow, int cus, hipStream_t st);
 
 // sketch_hh_stats.hip -- moments and order statistics of a set's current
 // estimates, all in integers.  One device record per
@@ -355,6 +366,10 @@ hipError_t launch_tally_query(const TallyTab &T, const TallyItems &I, uint64_t *
 hipError_t launch_tally_list(const TallyTab &T, uint64_t min_events, uint32_t cap, uint64_t *out_keys,
                              uint32_t *out_len, uint64_t *out_ev, uint64_t *out_va, unsigned int *out_n,
                              hipStream_t st);
+// the head takes another tally's refused counts: taken and dropped_events grow by dropped_events,
+// dropped_valid by dropped_valid, overflow != 0 sets the overflow word
+hipError_t launch_tally_head_add(const TallyTab &T, unsigned long long dropped_events,
+                                 unsigned long long dropped_valid, uint32_t overflow, hipStream_t st);
 
 // sketch_hll_fmt.hip -- HLL keys as Redis "HYLL" strings, one key per workgroup
 // (DESIGN.md section 14); the opcode rules are sketch_hll_fmt.h's

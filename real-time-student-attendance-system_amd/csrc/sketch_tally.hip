@@ -327,6 +327,19 @@ __global__ void __launch_bounds__(kTallyBlock) k_tally_list(const TallyTab T, ui
     out_va[at] = T.valid[slot];
 }
 
+// the head of a tally that takes another tally's entries takes its refused
+// counts too, so sum(events) + dropped_events == taken holds across the merge
+__global__ void k_tally_head_add(const TallyTab T, unsigned long long dropped_events,
+                                 unsigned long long dropped_valid, uint32_t overflow) {
+    if (blockIdx.x || threadIdx.x) return;
+    if (dropped_events) {
+        atomicAdd(T.taken, dropped_events);
+        atomicAdd(T.dropped_events, dropped_events);
+    }
+    if (dropped_valid) atomicAdd(T.dropped_valid, dropped_valid);
+    if (overflow) atomicOr(T.overflow, 1u);
+}
+
 constexpr size_t tally_lds_bytes(int lds_log2) { return (size_t(1) << lds_log2) * 20; }
 
 template <int kKind>
@@ -396,6 +409,13 @@ hipError_t launch_tally_list(const TallyTab &T, uint64_t min_events, uint32_t ca
     if (slots % kTallyBlock) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_tally_list, dim3(slots / kTallyBlock), dim3(kTallyBlock), 0, st, T, min_events, cap, out_keys,
                        out_len, out_ev, out_va, out_n);
+    return hipGetLastError();
+}
+
+hipError_t launch_tally_head_add(const TallyTab &T, unsigned long long dropped_events,
+                                 unsigned long long dropped_valid, uint32_t overflow, hipStream_t st) {
+    if (!dropped_events && !dropped_valid && !overflow) return hipSuccess;
+    hipLaunchKernelGGL(k_tally_head_add, dim3(1), dim3(64), 0, st, T, dropped_events, dropped_valid, overflow);
     return hipGetLastError();
 }
 

@@ -36,6 +36,13 @@ single-GPU run):
     (half the bytes of an all_reduce on the per-link-bound xGMI ring);
   * ``pfcount_each``   -- owner counts, one all_reduce(SUM) of u64 counts.
 
+The per-student and per-lecture counts (``analysis.StudentCounts``: Count-Min
+keys, heavy-hitter sets, the time profile, the lecture tally) are not sharded
+by key -- a student's swipes land on every rank that owns a lecture they
+attend -- so ``ShardedCounts`` replicates instead: a collective ``merge()``
+leaves the sum / union of every rank's state on every rank, in a second
+``StudentCounts`` that answers every query unchanged.
+
 The device operations are behind a small ``ops`` object so the collective
 logic runs unchanged with ``gloo`` on CPU tensors in the tests.
 """
@@ -1032,3 +1039,375 @@ def engine_k1(engine, fid: int = 0):
         return out
 
     return k1
+
+
+# ---- the per-student and per-lecture counts across ranks
+
+def _u64_bits(values) -> np.ndarray:
+    """Python ints below 2^64 as the int64 words a collective carries."""
+    return np.asarray([int(v) for v in values], dtype=np.uint64).view(np.int64)
+
+
+class Collectives:
+    """The two collectives ``ShardedCounts.merge`` is made of, as
+    ``ShardedSketch._all_reduce`` runs its own: device tensors under nccl, host
+    copies of device tensors under gloo, identities at world 1 (no process
+    group needed)."""
+
+    def __init__(self, rank: int, world: int, group=None):
+        import torch
+        import torch.distributed as dist
+        self.torch, self.dist = torch, dist
+        self.rank, self.world, self.group = rank, world, group
+        backend = dist.get_backend(group) if dist.is_initialized() else "gloo"
+        self.device_collectives = backend == "nccl"
+        self.solo = world == 1
+
+    def all_gather(self, t):
+        """``[world, *t.shape]``: every rank's ``t`` (equal shapes), on ``t``'s device."""
+        torch = self.torch
+        if self.solo:
+            return t.unsqueeze(0)
+        if self.device_collectives or t.device.type == "cpu":
+            out = torch.empty((self.world,) + tuple(t.shape), dtype=t.dtype, device=t.device)
+            self.dist.all_gather(list(out.unbind(0)), t.contiguous(), group=self.group)
+            return out
+        h = t.cpu().contiguous()
+        out = torch.empty((self.world,) + tuple(h.shape), dtype=h.dtype)
+        self.dist.all_gather(list(out.unbind(0)), h, group=self.group)
+        return out.to(t.device)
+
+    def all_reduce_sum(self, t):
+        if self.solo:
+            return t
+        if self.device_collectives or t.device.type == "cpu":
+            self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group)
+            return t
+        h = t.cpu()
+        self.dist.all_reduce(h, op=self.dist.ReduceOp.SUM, group=self.group)
+        t.copy_(h)
+        return t
+
+    def gather_ints(self, words, device) -> np.ndarray:
+        """``[world, len(words)]`` int64: every rank's small vector of words."""
+        t = self.torch.from_numpy(np.ascontiguousarray(words, dtype=np.int64))
+        if self.device_collectives and not self.solo:
+            t = t.to(device)
+        return self.all_gather(t).cpu().numpy()
+
+    def sum_ints(self, words, device) -> np.ndarray:
+        """The element-wise sum over the ranks of a small int64 vector."""
+        t = self.torch.from_numpy(np.array(words, dtype=np.int64))
+        if self.device_collectives and not self.solo:
+            t = t.to(device)
+        return self.all_reduce_sum(t).cpu().numpy()
+
+
+class LibsketchCountsOps:
+    """Device side of ``ShardedCounts`` (torch tensors on this rank's GPU): what
+    a ``StudentCounts`` holds, exported into tensors and merged from tensors.
+    Every library call is preceded by a torch synchronisation and the enqueue-only
+    merges are followed by ``sync()``: torch's stream and the context's are
+    different streams."""
+
+    def __init__(self, counts):
+        import torch
+        self.torch = torch
+        self.counts = counts
+        self.client = counts.client
+        self.device = torch.device("cuda", self.client.ctx.device)
+        c = counts
+        self.cms_keys = [c.attended_key, c.invalid_key] + ([c.late_key] if c.late_key is not None else [])
+        self.sets = [t[0] for t in c._tracks] + ([c._late_track[0]] if c._late_track is not None else [])
+        self.profile = c._profile
+        self.tally = c._lectures
+        self.view = None
+
+    # -- what must agree across the ranks, and the view
+    def _track(self, key):
+        name = b"hh:" + encode(key)
+        for t in self.counts._tracks + [self.counts._late_track]:
+            if t is not None and t[0] == name:
+                return t[1]
+        return None
+
+    def config(self) -> list:
+        """The table dimensions, ``late_from`` and the options, as integers."""
+        c, cl = self.counts, self.client
+        dims = []
+        for k in self.cms_keys:
+            i = cl.cms_info(k)
+            dims += [i["width"], i["depth"]]
+        dims += [0] * (6 - len(dims))
+        tracks = [self._track(k) or 0 for k in (c.attended_key, c.invalid_key)]
+        tracks.append((self._track(c.late_key) or 0) if c.late_key is not None else 0)
+        hh_log2 = max([cl.hh_info(s)["capacity"].bit_length() - 1 for s in self.sets], default=0)
+        tally_log2 = cl.tally_info(self.tally)["capacity"].bit_length() - 1 if self.tally is not None else 0
+        return [len(self.cms_keys)] + dims + [c.late_from] + tracks + [
+            int(self.profile is not None), int(c._day_insight), int(self.tally is not None), hh_log2, tally_log2]
+
+    def make_view(self, suffix, world: int, capacity_log2=None, lecture_capacity_log2=None):
+        """The merged view: a second ``StudentCounts`` on the same client whose
+        key, set, profile and tally names carry ``suffix``; its Count-Min keys
+        have the local keys' dimensions, its sets track at the threshold the
+        merged listing can promise, ``world * (t - 1) + 1``."""
+        from . import _lib
+        from .analysis import StudentCounts
+        c, cl = self.counts, self.client
+        sfx = encode(suffix)
+        cfg = self.config()
+        grow = (int(world) - 1).bit_length()  # ceil(log2(world))
+        for k in self.cms_keys:
+            if cl.keys.type_of(encode(k) + sfx) is None:
+                i = cl.cms_info(k)
+                cl.cms_initbydim(encode(k) + sfx, i["width"], i["depth"])
+        hh_log2 = capacity_log2 if capacity_log2 is not None else min(max(cfg[-2], _lib.SKE_HH_MIN_LOG2) + grow,
+                                                                        _lib.SKE_HH_MAX_LOG2)
+        tally_log2 = lecture_capacity_log2 if lecture_capacity_log2 is not None else \
+            min(max(cfg[-1], _lib.SKE_TALLY_MIN_LOG2) + grow, _lib.SKE_TALLY_MAX_LOG2)
+
+        def merged(t):
+            return None if t is None else int(world) * (t - 1) + 1
+        self.view = StudentCounts(
+            cl, attended_key=encode(c.attended_key) + sfx, invalid_key=encode(c.invalid_key) + sfx,
+            track_attended=merged(self._track(c.attended_key)), track_invalid=merged(self._track(c.invalid_key)),
+            capacity_log2=hh_log2, late_key=None if c.late_key is None else encode(c.late_key) + sfx,
+            late_from=c.late_from, track_late=None if c.late_key is None else merged(self._track(c.late_key)),
+            day_profile=self.profile + sfx if c._day_insight else None,
+            lecture_counts=None if self.tally is None else self.tally + sfx, lecture_capacity_log2=tally_log2)
+        return self.view
+
+    def _sync_torch(self):
+        self.torch.cuda.synchronize(self.device)
+
+    def _u8(self, nbytes: int):
+        return self.torch.zeros(max(int(nbytes), 16), dtype=self.torch.uint8, device=self.device)
+
+    def sync(self) -> None:
+        self.client.ctx.call("ske_sync")
+
+    # -- Count-Min tables
+    def cms_export(self, i: int):
+        """``(the table's cells padded to 16 bytes as a uint8 tensor, its count)``."""
+        cl, key = self.client, self.cms_keys[i]
+        p, ncells = cl.cms_table_dev(key)
+        nbytes = ((ncells + 3) & ~3) * 4
+        t = self._u8(nbytes)
+        self._sync_torch()
+        cl.ctx.call("ske_memcpy", C.c_void_p(t.data_ptr()), C.c_void_p(p), nbytes, 2)
+        return t[:nbytes], cl.cms_info(key)["count"]
+
+    def cms_sum(self, i: int, tables, counts) -> None:
+        """The view's key i = the saturating sum of ``tables`` ([ntables, bytes])."""
+        tables = tables.contiguous()
+        self._sync_torch()
+        self.client.cms_sum_dev(self.view_cms_keys()[i], tables, tables.shape[1] // 4, counts)
+        self.sync()  # the tables are torch's: they live until this call returns
+
+    def view_cms_keys(self):
+        v = self.view
+        return [v.attended_key, v.invalid_key] + ([v.late_key] if v.late_key is not None else [])
+
+    def view_sets(self):
+        v = self.view
+        return [t[0] for t in v._tracks] + ([v._late_track[0]] if v._late_track is not None else [])
+
+    # -- heavy-hitter sets
+    def hh_export(self, i: int):
+        """``(ids, lens, n, overflow)``: 16 n id bytes and 4 n length bytes as uint8 tensors."""
+        cl, name = self.client, self.sets[i]
+        cap = max(cl.hh_info(name)["used"], 1)
+        ids, lens = self._u8(cap * 16), self._u8(cap * 4)
+        self._sync_torch()
+        n, overflow = cl.hh_export_dev(name, ids, lens, cap)
+        return ids[:n * 16], lens[:n * 4], n, overflow
+
+    def hh_reset(self, i: int) -> None:
+        self.client.hh_reset(self.view_sets()[i])
+
+    def hh_merge(self, i: int, ids, lens, n: int, overflow: int) -> None:
+        self._sync_torch()
+        self.client.hh_merge_dev(self.view_sets()[i], ids if n else None, lens if n else None, n, overflow)
+
+    # -- the time profile
+    def tp_read(self) -> np.ndarray:
+        return self.client.tp_counts(self.profile).reshape(-1)
+
+    def tp_import(self, counts) -> None:
+        from .engine import tp_import
+        tp_import(self.client.ctx, self.client.tp_tid(self.view._profile), counts)
+
+    # -- the lecture tally
+    def tally_export(self):
+        """``(keys, lens, events, valid, n, dropped_events, dropped_valid,
+        overflow)``: 32 n, 4 n, 8 n and 8 n bytes as uint8 tensors, and the
+        head's words."""
+        cl = self.client
+        info = cl.tally_info(self.tally)
+        cap = max(info["used"], 1)
+        keys, lens, ev, va = self._u8(cap * 32), self._u8(cap * 4), self._u8(cap * 8), self._u8(cap * 8)
+        self._sync_torch()
+        n = cl.tally_export_dev(self.tally, keys, lens, ev, va, cap)
+        return (keys[:n * 32], lens[:n * 4], ev[:n * 8], va[:n * 8], n, info["dropped_events"],
+                info["dropped_valid"], info["overflow"])
+
+    def tally_reset(self) -> None:
+        self.client.tally_reset(self.view._lectures)
+
+    def tally_merge(self, keys, lens, events, valid, n: int, dropped_events: int, dropped_valid: int,
+                    overflow: int) -> None:
+        self._sync_torch()
+        none = n == 0
+        self.client.tally_merge_dev(self.view._lectures, None if none else keys, None if none else lens,
+                                    None if none else events, None if none else valid, n, dropped_events,
+                                    dropped_valid, overflow)
+
+
+class ShardedCounts:
+    """A ``StudentCounts`` whose swipes are spread over ``world`` ranks: the
+    insights of the whole run on every rank.
+
+    Replicate, do not partition.  Every rank counts the swipes it processes
+    into its local ``StudentCounts`` (``counts``), which this class never
+    touches otherwise.  The collective ``merge()`` leaves the same merged state
+    on every rank, in a second ``StudentCounts`` on the same client whose key,
+    set, profile and tally names carry ``suffix``: the saturating sum of the
+    ranks' Count-Min tables, the union of their heavy-hitter sets, the sum of
+    their time profiles and of their lecture tallies.  Nothing depends on how
+    the swipes were split, only on each swipe being counted on exactly one
+    rank.  The merged tables, profile and tally are then those one context fed
+    every swipe would hold, bit for bit.
+
+    Counting methods (``update``, ``count_packed``, ``update_messages*``,
+    ``timed``, ``counts_lectures``) go to the local object; the queries
+    (``attended``, ``invalid``, ``late``, ``top_*``, ``population``,
+    ``reference_threshold``, ``lecture_events``, ``lecture_rankings``,
+    ``by_day``, ``by_hour_of_week``) answer from the merged view as of the last
+    ``merge()``.  ``insights(**kw)`` is ``merge()`` followed by the view's
+    ``insights(**kw)``: it is COLLECTIVE -- every rank calls it at the same
+    point -- as ``merge()`` is and, for one small all-gather, the constructor.
+
+    The guarantee.  With the local sets tracked at threshold ``t`` over
+    ``world`` ranks, and the merged listing ``complete``, every id whose true
+    count reaches ``world * (t - 1) + 1`` is listed at any threshold at or above
+    that: some rank saw at least ``t`` of its swipes, so that rank's set holds
+    it, the union holds it, and its merged estimate is at least its true count.
+    The view refuses a list threshold below ``world * (t - 1) + 1``, as a
+    ``StudentCounts`` refuses one below ``t``.  At ``t = 1``, which the
+    ``"reference"`` rules need, the merged set is the whole population and the
+    merged statistics are exactly the one-context ones.
+
+    The view's set and tally capacities default to the local ``capacity_log2``
+    plus ``ceil(log2(world))``, capped at the build's maxima; a union that does
+    not fit leaves ``complete`` False.  The ranks' table dimensions,
+    ``late_from`` and options must agree, else ``ValueError`` on every rank.
+
+    The device operations sit behind ``ops`` (``LibsketchCountsOps``) and the
+    collectives behind ``transport`` (``Collectives``), so the gather, padding
+    and ordering logic runs under gloo on CPU tensors in the tests."""
+
+    _LOCAL = ("update", "count_packed", "update_messages", "update_messages_packed")
+    _VIEW = ("attended", "invalid", "late", "top_attended", "top_invalid", "top_late", "population",
+             "reference_threshold", "lecture_events", "lecture_rankings", "by_day", "by_hour_of_week")
+
+    def __init__(self, counts, rank: int, world: int, group=None, ops=None, transport=None, suffix="@all",
+                 capacity_log2: int | None = None, lecture_capacity_log2: int | None = None):
+        self.local = counts
+        self.rank, self.world = int(rank), int(world)
+        self.ops = ops if ops is not None else LibsketchCountsOps(counts)
+        self.transport = transport if transport is not None else Collectives(self.rank, self.world, group)
+        mine = [int(x) for x in self.ops.config()]
+        every = self.transport.gather_ints(mine, self.ops.device)
+        if any(row.tolist() != every[0].tolist() for row in every):
+            raise ValueError("ShardedCounts: the ranks' table dimensions, late_from and options differ: "
+                             + "; ".join(f"rank {r}: {row.tolist()}" for r, row in enumerate(every)))
+        self.view = self.ops.make_view(suffix, self.world, capacity_log2, lecture_capacity_log2)
+        self.merges = 0
+
+    @property
+    def timed(self) -> bool:
+        return self.local.timed
+
+    @property
+    def counts_lectures(self) -> bool:
+        return self.local.counts_lectures
+
+    def _pad(self, t, nbytes: int):
+        """``t`` (uint8) as ``nbytes`` bytes, zero filled behind it."""
+        out = t.new_zeros(nbytes)
+        out[:t.numel()] = t
+        return out
+
+    def merge(self) -> None:
+        """COLLECTIVE.  Rebuild the merged view from every rank's local state;
+        the view is overwritten, never added to, so a second ``merge()`` with
+        nothing counted in between leaves it as it was."""
+        import torch
+        ops, tr, world = self.ops, self.transport, self.world
+        n_cms, n_sets = len(ops.cms_keys), len(ops.sets)
+        # every local export first, then one all-gather of the sizes and head words
+        tables = [ops.cms_export(i) for i in range(n_cms)]
+        sets = [ops.hh_export(i) for i in range(n_sets)]
+        tally = ops.tally_export() if ops.tally is not None else None
+        words = [c for _, c in tables]
+        for s in sets:
+            words += [s[2], s[3]]
+        if tally is not None:
+            words += list(tally[4:])
+        meta = tr.gather_ints(_u64_bits(words), ops.device).view(np.uint64)
+        col = 0
+        for i, (t, _) in enumerate(tables):
+            ops.cms_sum(i, tr.all_gather(t), meta[:, col])
+            col += 1
+        for i, (ids, lens, _, _) in enumerate(sets):
+            ns, ovs = meta[:, col], meta[:, col + 1]
+            col += 2
+            # padded to the largest rank, a multiple of 4 entries so that every
+            # rank's segment starts on a 16-byte boundary
+            nmax = (int(ns.max()) + 3) & ~3
+            ops.hh_reset(i)
+            got = tr.all_gather(torch.cat([self._pad(ids, 16 * nmax), self._pad(lens, 4 * nmax)])) if nmax else None
+            for r in range(world):
+                n = int(ns[r])
+                ops.hh_merge(i, got[r, :16 * nmax] if n else None, got[r, 16 * nmax:] if n else None, n, int(ovs[r]))
+            ops.sync()
+        if ops.profile is not None:
+            mine = np.ascontiguousarray(ops.tp_read(), dtype=np.uint64).view(np.int64)
+            ops.tp_import(tr.sum_ints(mine, ops.device).view(np.uint64))
+        if tally is not None:
+            keys, lens, ev, va = tally[:4]
+            ns, dev_, dva, ovs = (meta[:, col + j] for j in range(4))
+            nmax = (int(ns.max()) + 3) & ~3
+            ops.tally_reset()
+            got = None
+            if nmax:
+                got = tr.all_gather(torch.cat([self._pad(keys, 32 * nmax), self._pad(ev, 8 * nmax),
+                                               self._pad(va, 8 * nmax), self._pad(lens, 4 * nmax)]))
+            for r in range(world):
+                n = int(ns[r])
+                seg = (None,) * 4 if not n else (got[r, :32 * nmax], got[r, 48 * nmax:], got[r, 32 * nmax:40 * nmax],
+                                                 got[r, 40 * nmax:48 * nmax])
+                ops.tally_merge(*seg, n, int(dev_[r]), int(dva[r]), int(ovs[r]))
+            ops.sync()
+        self.merges += 1
+
+    def insights(self, **kw) -> list:
+        """COLLECTIVE: ``merge()``, then the merged view's ``insights(**kw)``."""
+        self.merge()
+        return self.view.insights(**kw)
+
+
+def _delegate(target: str, name: str):
+    def call(self, *a, **kw):
+        return getattr(getattr(self, target), name)(*a, **kw)
+    call.__name__ = name
+    call.__doc__ = f"``StudentCounts.{name}`` of the " + ("local counts." if target == "local" else
+                                                          "merged view, as of the last ``merge()``.")
+    return call
+
+
+for _n in ShardedCounts._LOCAL:
+    setattr(ShardedCounts, _n, _delegate("local", _n))
+for _n in ShardedCounts._VIEW:
+    setattr(ShardedCounts, _n, _delegate("view", _n))
+del _n
