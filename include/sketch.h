@@ -30,7 +30,8 @@
  *     keys by a caller-chosen register-slab slot, Count-Min Sketch tables by a
  *     caller-chosen `cid` < SKE_MAX_CMS, heavy-hitter sets by a caller-chosen
  *     `hid` < SKE_MAX_HH, time profiles by a caller-chosen `tid` < SKE_MAX_TP,
- *     tallies by a caller-chosen `tid` < SKE_MAX_TALLY (a space of their own).
+ *     tallies by a caller-chosen `tid` < SKE_MAX_TALLY, seen-row sets by a
+ *     caller-chosen `sid` < SKE_MAX_SEEN (spaces of their own).
  *     The facade maps Redis key names to fids / slots /
  *     cids.
  */
@@ -80,6 +81,11 @@ extern "C" {
 #define SKE_ETALLYEXISTS -33 /* ske_tally_init on an id in use */
 #define SKE_ETALLYCAP -34    /* capacity_log2 outside [SKE_TALLY_MIN_LOG2, SKE_TALLY_MAX_LOG2] */
 #define SKE_ETALLYSPACE -35  /* ske_tally_list: more entries pass than the output arrays hold */
+/* -36 is not assigned */
+#define SKE_ESEENNOSET -37   /* seen set id not in use */
+#define SKE_ESEENEXISTS -38  /* ske_seen_init on an id in use */
+#define SKE_ESEENCAP -39     /* capacity_log2 outside [SKE_SEEN_MIN_LOG2, SKE_SEEN_MAX_LOG2] */
+#define SKE_ESEENCALLS -40   /* the set's 32-bit call counter would wrap: ske_seen_reset starts it again */
 
 #define SKE_MEM_HOST 0
 #define SKE_MEM_DEVICE 1
@@ -106,6 +112,14 @@ extern "C" {
 #define SKE_TALLY_MAX_PROBES 128 /* slots one insert-or-add looks at before it gives up */
 #define SKE_TALLY_LOAD_DEN 2   /* new keys are refused once used >= capacity / SKE_TALLY_LOAD_DEN */
 #define SKE_TALLY_MAX_TOP 16   /* entries per end one ske_tally_top returns */
+#define SKE_MAX_SEEN 256
+#define SKE_SEEN_MIN_LOG2 8
+#define SKE_SEEN_MAX_LOG2 30
+#define SKE_SEEN_MAX_PROBES 128 /* slots one walk looks at before it gives up */
+#define SKE_SEEN_LOAD_DEN 2    /* new keys find no slot once used >= capacity / SKE_SEEN_LOAD_DEN */
+#define SKE_SEEN_FIRST 0       /* ske_seen_add's answer bytes: count this row, */
+#define SKE_SEEN_REPEAT 1      /*   a repeat, */
+#define SKE_SEEN_SKIPPED 2     /*   the mask kept the item out */
 #define SKE_HLL_REGISTERS 16384
 #define SKE_HLL_DENSE_BYTES 12288
 #define SKE_HLL_DUMP_MAX_KEYS (1u << 18)   /* 2^18 * 12304 B < 2^32: u32 offsets suffice */
@@ -623,6 +637,87 @@ int ske_tally_merge_dev(ske_ctx *ctx, uint32_t tid, const uint8_t *keys_dev, con
                         const uint64_t *events_dev, const uint64_t *valid_dev, uint64_t n, uint64_t dropped_events,
                         uint64_t dropped_valid, uint32_t foreign_overflow);
 
+/* ---- seen-row sets: count each row once under redelivery ----
+ * An exact, insert-only set of 128-bit row keys on the device whose add
+ * answers, per item, first sighting or repeat.  The counters (Count-Min, time
+ * profile, tallies) add 1 per item, so a redelivered batch counts twice; the
+ * reference's analytics do not, they read Cassandra rows keyed (lecture_id,
+ * timestamp, student_id), where a redelivered row overwrites itself
+ * (attendance_processor.py:64-72, :134-136).  The answer bytes of an add are
+ * usable as a status column: 0 means count it.
+ *
+ * Keys.  A key is two u64 words, item i at keys[2i], keys[2i + 1]; keys_dev is
+ * 16-byte aligned and holds 2n words.  A fold with begin != 0 starts every key
+ * at two fixed seeds, else at the words that are there; folding a column
+ * replaces each word k by MurmurHash64A(the item's column bytes, seed = k).  A
+ * row is whatever the caller folds, in that order; the attendance row is the
+ * lecture bytes, the id bytes, then the 8 little-endian bytes of int64
+ * floor(epoch / granularity) (granularity >= 1; the floor also for a negative
+ * epoch; 1: the row of the reference, 86400: one per UTC day).  The set reads a
+ * word 0 as 1 (0 marks an empty slot).  Two rows are the same when their keys
+ * are: an accidental match needs a 128-bit collision.
+ *   packed: column item i = bytes[offs[i] .. offs[i + 1]) (bytes readable to the
+ *     next 8-byte boundary behind the last item);
+ *   fixed: the `width` bytes at bytes + i * width (width 0: the empty string);
+ *   spans: bytes[start[j] .. start[j] + len[j]) with j = at[i], or i when at is
+ *     NULL -- a column of ske_ingest_parse read in place.  Only the aligned
+ *     8-byte words that hold a byte of the item are read.
+ * All four are enqueue only and graph-capturable; n < 2^32 - 1.
+ *
+ * The set.  2^capacity_log2 slots of 24 bytes, addressed by a caller-chosen
+ * sid < SKE_MAX_SEEN; the context owns it.  Linear probing from the low bits of
+ * the first word; a walk looks at SKE_SEEN_MAX_PROBES slots, and new keys find
+ * no slot once capacity / SKE_SEEN_LOAD_DEN are used (`limit`; the adds in flight
+ * at that moment may pass it, the capacity never).  An item that finds no slot is
+ * answered SKE_SEEN_FIRST and counted in `unplaced`: the set fails open, a count
+ * is never lost and a SKE_SEEN_REPEAT is never false.  While unplaced is 0 the
+ * answers are exact and identical from run to run.  Nothing is removed one by
+ * one; ske_seen_reset empties the set. */
+typedef struct {
+    uint64_t capacity;   /* slots */
+    uint64_t limit;      /* keys it takes: capacity / SKE_SEEN_LOAD_DEN */
+    uint64_t used;       /* keys held */
+    uint64_t calls;      /* adds run so far (those with n > 0; replays of a recorded add included) */
+    uint64_t looked_at;  /* items the masks let through */
+    uint64_t first;      /* of those, answered SKE_SEEN_FIRST (the unplaced ones included) */
+    uint64_t unplaced;   /* of those, the ones that found no slot */
+} ske_seen_info_t;
+/* empty; SKE_ESEENEXISTS when sid is in use, SKE_ESEENCAP for a capacity out of range */
+int ske_seen_init(ske_ctx *ctx, uint32_t sid, uint32_t capacity_log2);
+/* SKE_EBUSY while a recorded graph is alive or being recorded */
+int ske_seen_free(ske_ctx *ctx, uint32_t sid);
+/* an empty set again, its counts and its call counter zeroed */
+int ske_seen_reset(ske_ctx *ctx, uint32_t sid);
+int ske_seen_info(ske_ctx *ctx, uint32_t sid, ske_seen_info_t *out);
+int ske_seen_fold_packed_async(ske_ctx *ctx, uint64_t *keys_dev, const uint8_t *bytes_dev, const uint32_t *offs_dev,
+                               uint64_t n, int begin);
+int ske_seen_fold_fixed_async(ske_ctx *ctx, uint64_t *keys_dev, const uint8_t *bytes_dev, uint32_t width, uint64_t n,
+                              int begin);
+int ske_seen_fold_spans_async(ske_ctx *ctx, uint64_t *keys_dev, const uint8_t *bytes_dev, const uint32_t *start_dev,
+                              const uint32_t *len_dev, const uint32_t *at_or_null, uint64_t n, int begin);
+int ske_seen_fold_epoch_async(ske_ctx *ctx, uint64_t *keys_dev, const int64_t *epoch_dev, int64_t granularity,
+                              uint64_t n, int begin);
+/* One batch of keys on the device, enqueue only and graph-capturable; n < 2^32 - 1.
+ * out_dev[i] =
+ *   SKE_SEEN_SKIPPED  mask_or_null is given and mask[i] != want: the key is not inserted;
+ *   SKE_SEEN_FIRST    the key was not in the set before this call and i is the
+ *                     lowest index among this call's items with that key;
+ *   SKE_SEEN_REPEAT   otherwise.
+ * After the call every key that was let through is in the set (unless it found
+ * no slot).  Each call takes the next number of the set's 32-bit call counter,
+ * which lives on the device, so a recorded add sees a new call at every replay;
+ * SKE_ESEENCALLS once the numbers run out.  The per-item state between the
+ * call's kernels is context scratch: record the call after one direct call of at
+ * least its size. */
+int ske_seen_add_async(ske_ctx *ctx, uint32_t sid, const uint64_t *keys_dev, uint64_t n, const uint8_t *mask_or_null,
+                       int want, uint8_t *out_dev);
+/* present_out[i] = 1 when key i is in the set, else 0; nothing is inserted.  Enqueue only, capturable. */
+int ske_seen_test_async(ske_ctx *ctx, uint32_t sid, const uint64_t *keys_dev, uint64_t n, uint8_t *present_out);
+/* The same over host or device arrays (mem covers keys, mask and the output); return when done. */
+int ske_seen_add(ske_ctx *ctx, uint32_t sid, const uint64_t *keys, uint64_t n, const uint8_t *mask_or_null, int want,
+                 uint8_t *out, int mem);
+int ske_seen_test(ske_ctx *ctx, uint32_t sid, const uint64_t *keys, uint64_t n, uint8_t *present_out, int mem);
+
 /* ---- the fused hot path (K1) ----
  * For every swipe i: v = BF.EXISTS fid id_i; if v: PFADD slot_i id_i.
  *   replaces the per-event pair attendance_processor.py:109-113 + :127-129.
@@ -838,6 +933,8 @@ int ske_ingest_dense(ske_ctx *ctx, const uint8_t *msgs, const ske_ingest_cols_t 
  * ske_swipes_fixed_async, ske_cms_add_fixed_async, ske_cms_add_packed_async,
  * ske_hh_track_fixed_async, ske_hh_track_packed_async, ske_tp_add_async,
  * ske_tally_add_packed_async, ske_tally_add_fixed_async, ske_tally_add_spans_async,
+ * ske_seen_fold_packed_async, ske_seen_fold_fixed_async, ske_seen_fold_spans_async,
+ * ske_seen_fold_epoch_async, ske_seen_add_async, ske_seen_test_async,
  * ske_ingest_times) into an executable graph, uploaded to the device;
  * each ske_graph_launch replays it on the context stream.  A consumer that
  * processes a ring of fixed device batch slots replays one graph per turn of

@@ -49,6 +49,10 @@ SKE_ETALLYNOSET = -32
 SKE_ETALLYEXISTS = -33
 SKE_ETALLYCAP = -34
 SKE_ETALLYSPACE = -35
+SKE_ESEENNOSET = -37
+SKE_ESEENEXISTS = -38
+SKE_ESEENCAP = -39
+SKE_ESEENCALLS = -40
 SKE_MEM_HOST = 0
 SKE_MEM_DEVICE = 1
 SKE_MAX_FILTERS = 4096
@@ -70,6 +74,14 @@ SKE_TALLY_MAX_LOG2 = 24
 SKE_TALLY_MAX_PROBES = 128
 SKE_TALLY_LOAD_DEN = 2
 SKE_TALLY_MAX_TOP = 16
+SKE_MAX_SEEN = 256
+SKE_SEEN_MIN_LOG2 = 8
+SKE_SEEN_MAX_LOG2 = 30
+SKE_SEEN_MAX_PROBES = 128
+SKE_SEEN_LOAD_DEN = 2
+SKE_SEEN_FIRST = 0
+SKE_SEEN_REPEAT = 1
+SKE_SEEN_SKIPPED = 2
 HLL_REGISTERS = 16384
 HLL_DENSE_BYTES = 12288
 SKE_HLL_DUMP_MAX_KEYS = 1 << 18
@@ -115,6 +127,12 @@ class TallyInfo(C.Structure):
     """ske_tally_info_t (include/sketch.h)."""
     _fields_ = [("capacity", C.c_uint64), ("used", C.c_uint64), ("overflow", C.c_uint64), ("taken", C.c_uint64),
                 ("dropped_events", C.c_uint64), ("dropped_valid", C.c_uint64)]
+
+
+class SeenInfo(C.Structure):
+    """ske_seen_info_t (include/sketch.h)."""
+    _fields_ = [("capacity", C.c_uint64), ("limit", C.c_uint64), ("used", C.c_uint64), ("calls", C.c_uint64),
+                ("looked_at", C.c_uint64), ("first", C.c_uint64), ("unplaced", C.c_uint64)]
 
 
 class IngestCols(C.Structure):
@@ -240,6 +258,18 @@ SIGNATURES = {
                                        C.POINTER(C.c_uint64)]),
     "ske_tally_merge_dev": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, _u64p, _u64p, C.c_uint64, C.c_uint64,
                                       C.c_uint64, C.c_uint32]),
+    "ske_seen_init": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),
+    "ske_seen_free": (C.c_int, [_CTX, C.c_uint32]),
+    "ske_seen_reset": (C.c_int, [_CTX, C.c_uint32]),
+    "ske_seen_info": (C.c_int, [_CTX, C.c_uint32, C.POINTER(SeenInfo)]),
+    "ske_seen_fold_packed_async": (C.c_int, [_CTX, _u64p, _u8p, _u32p, C.c_uint64, C.c_int]),
+    "ske_seen_fold_fixed_async": (C.c_int, [_CTX, _u64p, _u8p, C.c_uint32, C.c_uint64, C.c_int]),
+    "ske_seen_fold_spans_async": (C.c_int, [_CTX, _u64p, _u8p, _u32p, _u32p, _u32p, C.c_uint64, C.c_int]),
+    "ske_seen_fold_epoch_async": (C.c_int, [_CTX, _u64p, _vp, C.c_int64, C.c_uint64, C.c_int]),
+    "ske_seen_add_async": (C.c_int, [_CTX, C.c_uint32, _u64p, C.c_uint64, _u8p, C.c_int, _u8p]),
+    "ske_seen_test_async": (C.c_int, [_CTX, C.c_uint32, _u64p, C.c_uint64, _u8p]),
+    "ske_seen_add": (C.c_int, [_CTX, C.c_uint32, _u64p, C.c_uint64, _u8p, C.c_int, _u8p, C.c_int]),
+    "ske_seen_test": (C.c_int, [_CTX, C.c_uint32, _u64p, C.c_uint64, _u8p, C.c_int]),
     "ske_swipes": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p, C.c_int]),
     "ske_swipes_async": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p]),
     "ske_swipes_fixed": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, C.c_uint32, C.c_uint64, _u8p,

@@ -28,6 +28,12 @@ The reference has none of this as arrays; it has JSON messages.
 timestamps included, and the decoded ids, answers and times feed the same
 counters in place (DESIGN.md "Insights from the message stream");
 ``count_packed`` is the counting alone, for swipes already answered.
+
+Every counter adds one per row it is given, and an at-least-once transport
+gives some rows twice.  With ``dedup`` set, a seen-row set (client_seen.py,
+DESIGN.md "Seen rows") answers per row whether it was counted before, and only
+first sightings reach the counters -- the reference's analytics read a
+Cassandra table in which a redelivered row overwrites itself.
 """
 from __future__ import annotations
 
@@ -37,7 +43,7 @@ from datetime import datetime, timedelta, timezone
 
 import numpy as np
 
-from ._lib import IngestDense, SKE_MEM_DEVICE
+from ._lib import IngestCols, IngestDense, SKE_MEM_DEVICE, SKE_SEEN_FIRST
 from .client_ingest import join_messages
 from .encoding import encode, pack
 from .engine import DeviceBuffer, hh_list, tally_query
@@ -135,14 +141,33 @@ class StudentCounts:
     is the text ``keyspace.day_key`` puts into the key name,
     ``str(lecture_id).encode()``, at most 32 bytes.  With it set ``update`` and
     ``count_packed`` need the swipes' ``lectures``; ``update_messages`` reads
-    them from the messages."""
+    them from the messages.
+
+    ``dedup`` (default None: off): the name of a seen-row set
+    (``client.seen_create``; made here with ``2 ** dedup_capacity_log2`` slots
+    when it does not exist).  The counting half of ``update``, ``count_packed``
+    and ``update_messages`` then counts a row -- (lecture, id,
+    ``floor(epoch / dedup_granularity)``) -- only at its first sighting, so a
+    redelivered row counts once, as it does in the reference's Cassandra table
+    (``PRIMARY KEY ((lecture_id), timestamp, student_id)``,
+    attendance_processor.py:64-72).  ``dedup_granularity=86400`` counts a
+    student once per lecture and UTC day.  The swipe half (BF.EXISTS, PFADD)
+    still runs on every row and the returned validity is unchanged.  With it
+    set the counting calls need the swipes' times and lectures whether or not
+    the time and lecture options are on (``needs_times`` / ``needs_lectures``).
+    A set that is full answers "first": a count is never lost."""
 
     def __init__(self, client, attended_key="cms:attended", invalid_key="cms:invalid",
                  error: float = 0.001, probability: float = 0.01, track_attended: int | None = None,
                  track_invalid: int | None = None, capacity_log2: int = 16, late_key=None,
                  late_from: int = 9 * 3600, track_late: int | None = None, day_profile=None,
-                 lecture_counts=None, lecture_capacity_log2: int = 16):
+                 lecture_counts=None, lecture_capacity_log2: int = 16, dedup=None,
+                 dedup_capacity_log2: int = 22, dedup_granularity: int = 1):
         self.client = client
+        self._dedup = encode(dedup) if dedup is not None else None
+        self._dedup_gran = int(dedup_granularity)
+        if self._dedup_gran < 1:
+            raise ValueError("dedup_granularity is at least 1 second")
         self._lectures = encode(lecture_counts) if lecture_counts is not None else None
         self._lec_bufs = None
         self.attended_key, self.invalid_key = attended_key, invalid_key
@@ -183,6 +208,8 @@ class StudentCounts:
                 client.tp_create(self._profile)
         if self._lectures is not None and self._lectures not in client._tally:
             client.tally_create(self._lectures, lecture_capacity_log2)
+        if self._dedup is not None and self._dedup not in client._seen:
+            client.seen_create(self._dedup, dedup_capacity_log2)
 
     def _buffers(self, n: int, width: int):
         b = self._bufs
@@ -203,8 +230,8 @@ class StudentCounts:
         """The swipes' lectures as a packed batch ``(buf, offs)`` (None when
         the option is off): a packed pair is taken as it is, a sequence is
         encoded as ``keyspace.day_key`` names the lecture, ``str(x).encode()``."""
-        if (lectures is None) != (self._lectures is None):
-            raise ValueError("lectures go with lecture_counts: required with it, refused without")
+        if (lectures is None) != (not self.needs_lectures):
+            raise ValueError("lectures go with lecture_counts (or dedup): required with it, refused without")
         if lectures is None:
             return None
         if isinstance(lectures, tuple) and len(lectures) == 2 and isinstance(lectures[1], np.ndarray):
@@ -253,16 +280,12 @@ class StudentCounts:
         if ids.ndim != 2:
             raise ValueError("ids must be a [n, width] uint8 array")
         n, width = ids.shape
-        if (times is None) != (self._profile is None):
-            raise ValueError("times go with late_key / day_profile: required with either, refused without")
-        ep = None
-        if times is not None:
-            ep = epoch_seconds(times)
-            if ep.size != n:
-                raise ValueError("one time per id")
+        ep = self._check_times(times, n)
         lec = self._check_lectures(lectures, n)
         if n == 0 or width == 0:
             return np.zeros(n, bool)
+        if self._dedup is not None:
+            return self._update_dedup(bf_key, slots, ids, ep, lec)
         s = np.ascontiguousarray(slots, dtype=np.uint32)
         if s.shape != (n,):
             raise ValueError("one slot per id")
@@ -313,6 +336,82 @@ class StudentCounts:
         """Whether the counting calls take the swipes' lectures (``lecture_counts``)."""
         return self._lectures is not None
 
+    @property
+    def dedup(self) -> bool:
+        """Whether a seen-row set keeps repeats out of the counts (``dedup``)."""
+        return self._dedup is not None
+
+    @property
+    def needs_times(self) -> bool:
+        """Whether the counting calls need the swipes' times: for a profile
+        (``timed``) or for the row keys of ``dedup``."""
+        return self._profile is not None or self._dedup is not None
+
+    @property
+    def needs_lectures(self) -> bool:
+        """Whether the counting calls need the swipes' lectures: for the tally
+        (``counts_lectures``) or for the row keys of ``dedup``."""
+        return self._lectures is not None or self._dedup is not None
+
+    def duplicate_rows(self) -> int:
+        """Rows the seen set kept out of the counts so far: ``looked_at - first``."""
+        if self._dedup is None:
+            raise ValueError("no dedup")
+        info = self.client.seen_info(self._dedup)
+        return info["looked_at"] - info["first"]
+
+    def _first_sightings(self, buf, offs, ep, lec) -> np.ndarray:
+        """The rows' keys folded on the device, added to the seen set: bool per
+        row, True where it is to be counted."""
+        cl = self.client
+        n = ep.size
+        b = cl.seen_fold_rows_packed((buf, offs), ep, lec, self._dedup_gran)
+        cl.ctx.call("ske_seen_add_async", cl.seen_sid(self._dedup), C.c_void_p(b["keys"].ptr), n, None, 0,
+                    C.c_void_p(b["out"].ptr))
+        cl.ctx.call("ske_sync")
+        return b["out"].to_host(np.uint8, n) == SKE_SEEN_FIRST
+
+    @staticmethod
+    def _take_packed(buf, offs, keep):
+        """The kept items of a packed batch, packed again."""
+        lens = np.diff(offs.astype(np.int64))
+        body = buf[int(offs[0]):int(offs[-1])]
+        out = np.zeros(int(keep.sum()) + 1, np.uint32)
+        np.cumsum(lens[keep], out=out[1:])
+        return np.ascontiguousarray(body[np.repeat(keep, lens)]), out
+
+    def _count_first(self, buf, offs, v, ep, lec) -> None:
+        """``dedup``: the rows seen before leave, the others take the counting
+        path.  The time and lecture columns go on only where their option is on."""
+        keep = self._first_sightings(buf, offs, ep, lec)
+        if not keep.any():
+            return
+        if not keep.all():
+            buf, offs = self._take_packed(buf, offs, keep)
+            v, ep, lec = v[keep], ep[keep], self._take_packed(lec[0], lec[1], keep)
+        self._count_kept(buf, offs, v, ep if self.timed else None, lec if self.counts_lectures else None)
+
+    def _update_dedup(self, bf_key, slots, ids, ep, lec) -> np.ndarray:
+        """``update`` with ``dedup``: the swipe call over every row, then the
+        counting over the first sightings (host-fed, as ``count_packed``)."""
+        cl = self.client
+        n, width = ids.shape
+        s = np.ascontiguousarray(slots, dtype=np.uint32)
+        if s.shape != (n,):
+            raise ValueError("one slot per id")
+        d_ids, d_slots, d_valid, *_ = self._buffers(n, width)
+        bkey = encode(bf_key)
+        valid = np.zeros(n, np.uint8)  # BF.EXISTS of a missing key answers 0
+        if cl.keys.expect(bkey, "bf"):
+            d_ids.from_host(ids)
+            d_slots.from_host(s)
+            cl.ctx.call("ske_swipes_fixed", cl.keys.fid[bkey], C.c_void_p(d_slots.ptr), C.c_void_p(d_ids.ptr),
+                        width, n, C.c_void_p(d_valid.ptr), SKE_MEM_DEVICE)
+            valid = d_valid.to_host(np.uint8, n)
+        offs = (np.arange(n + 1, dtype=np.uint64) * width).astype(np.uint32)
+        self._count_first(ids.reshape(-1), offs, valid, ep, lec)
+        return valid.astype(bool)
+
     def _enqueue_packed(self, d_ids, d_offs, n: int, d_valid, d_epoch, d_late) -> None:
         """The counting half of ``update`` over a packed batch on the device
         (id i = ``ids[offs[i]:offs[i + 1]]``), enqueued in ``update``'s order:
@@ -358,12 +457,15 @@ class StudentCounts:
             if which == "dense":  # every message's epoch before compaction; the entries' message indices
                 b["epoch_all"] = DeviceBuffer(ctx, cn * 8 + 16)
                 b["at"] = DeviceBuffer(ctx, cn * 4 + 16)
+                if self._dedup is not None:  # every message's row key and the set's answer
+                    b["seen_keys"] = DeviceBuffer(ctx, cn * 16 + 16)
+                    b["seen_out"] = DeviceBuffer(ctx, cn + 16)
             self._pk_bufs[which] = b
         return b
 
     def _check_times(self, times, n: int):
-        if (times is None) != (self._profile is None):
-            raise ValueError("times go with late_key / day_profile: required with either, refused without")
+        if (times is None) != (not self.needs_times):
+            raise ValueError("times go with late_key / day_profile (or dedup): required with either, refused without")
         if times is None:
             return None
         ep = epoch_seconds(times)
@@ -388,6 +490,14 @@ class StudentCounts:
         lec = self._check_lectures(lectures, n)
         if n == 0:
             return
+        if self._dedup is not None:
+            self._count_first(buf, offs, v, ep, lec)
+        else:
+            self._count_kept(buf, offs, v, ep, lec)
+
+    def _count_kept(self, buf, offs, v, ep, lec) -> None:
+        """``count_packed``'s work over checked arrays."""
+        n = offs.size - 1
         b = self._packed_buffers("host", n, int(offs[-1]))
         b["ids"].from_host(buf[:int(offs[-1])])
         b["offs"].from_host(offs)
@@ -427,11 +537,24 @@ class StudentCounts:
         B, n = run.B, run.n
         d = self._packed_buffers("dense", n, B["msgs"].nbytes)  # an id is a piece of its message
         msgs = C.c_void_p(B["msgs"].ptr)
-        if self.timed:
+        if self.needs_times:
             cl.ctx.call("ske_ingest_times", msgs, C.byref(run.cols), n, C.c_void_p(d["epoch_all"].ptr))
+        cols = run.cols
+        if self._dedup is not None:
+            # The row keys from the parse columns in place, per message; the
+            # set's answer bytes then stand in for the status column: 0 is a
+            # decoded message whose row is new, so the repeats leave with the
+            # undecoded ones and nothing is compacted.
+            keys, seen_out = C.c_void_p(d["seen_keys"].ptr), C.c_void_p(d["seen_out"].ptr)
+            cl.ctx.call("ske_seen_fold_spans_async", keys, msgs, cols.lec_start, cols.lec_len, None, n, 1)
+            cl.ctx.call("ske_seen_fold_spans_async", keys, msgs, cols.id_start, cols.id_len, None, n, 0)
+            cl.ctx.call("ske_seen_fold_epoch_async", keys, C.c_void_p(d["epoch_all"].ptr), self._dedup_gran, n, 0)
+            cl.ctx.call("ske_seen_add_async", cl.seen_sid(self._dedup), keys, n, cols.status, 0, seen_out)
+            cols = IngestCols.from_buffer_copy(run.cols)
+            cols.status = d["seen_out"].ptr
         out = IngestDense(*[C.c_void_p(d[k].ptr) for k in ("ids", "offs", "epoch", "valid", "at")])
         ndense, nbytes = C.c_uint64(), C.c_uint64()
-        cl.ctx.call("ske_ingest_dense", msgs, C.byref(run.cols), n,
+        cl.ctx.call("ske_ingest_dense", msgs, C.byref(cols), n,
                     C.c_void_p(B["valid"].ptr) if run.has_bf else None,  # a missing key answers 0
                     C.c_void_p(d["epoch_all"].ptr) if self.timed else None, C.byref(out), d["nbytes"],
                     C.byref(ndense), C.byref(nbytes))
@@ -439,14 +562,15 @@ class StudentCounts:
             self._enqueue_packed(d["ids"], d["offs"], int(ndense.value), d["valid"],
                                  d["epoch"] if self.timed else None, d["late"])
             if self._lectures is not None:  # the lecture spans of the parse columns, in place
-                cl.ctx.call("ske_tally_add_spans_async", cl.tally_tid(self._lectures), msgs, run.cols.lec_start,
-                            run.cols.lec_len, n, run.cols.status,
+                cl.ctx.call("ske_tally_add_spans_async", cl.tally_tid(self._lectures), msgs, cols.lec_start,
+                            cols.lec_len, n, cols.status,
                             C.c_void_p(B["valid"].ptr) if run.has_bf else None)
             cl.ctx.call("ske_sync")
         if run.host_at:
             hbuf, hoffs = pack(run.host_ids)
-            self.count_packed(hbuf, hoffs, valid[np.asarray(run.host_at)], run.host_ts if self.timed else None,
-                              run.host_lectures if self._lectures is not None else None)
+            self.count_packed(hbuf, hoffs, valid[np.asarray(run.host_at)],
+                              run.host_ts if self.needs_times else None,
+                              run.host_lectures if self.needs_lectures else None)
         return valid, status
 
     def _query(self, key, ids) -> np.ndarray:

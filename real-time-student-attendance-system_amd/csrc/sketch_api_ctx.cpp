@@ -1,7 +1,7 @@
 // sketch_api_ctx.cpp -- libsketch C-ABI (include/sketch.h): the context's
 // lifecycle, options, the sticky error word, streams, host -> device staging,
 // pass timing, the scratch-use ordering and graph capture.  The other
-// subsystems are sketch_api_{bloom,hll,swipes,ingest,cms,hh,tp,tally}.cpp (map: sketch_ctx.h).
+// subsystems are sketch_api_{bloom,hll,swipes,ingest,cms,hh,tp,tally,seen}.cpp (map: sketch_ctx.h).
 #include <stdlib.h>
 #include <string.h>
 
@@ -173,13 +173,18 @@ static int scratch_user_begin(ske_ctx *c, ScratchUse &u, hipStream_t st, unsigne
     return SKE_OK;
 }
 
+// the bit of a group in ske_ctx::cap_users / graph_users
+static unsigned scratch_use_bit(const ske_ctx *c, const ScratchUse *u) {
+    return u == &c->sn ? 4u : u == &c->rt ? 2u : 1u;
+}
+
 ScratchUser::ScratchUser(ske_ctx *c, ScratchUse &u, hipStream_t st) : c_(c), u_(u), st_(st) {
     rc = scratch_user_begin(c, u, st, &cid_);
 }
 
 ScratchUser::~ScratchUser() {
     if (rc) return;
-    if (cid_) c_->cap_users |= &u_ == &c_->rt ? 2u : 1u;
+    if (cid_) c_->cap_users |= scratch_use_bit(c_, &u_);
     u_.stream = st_;
     u_.cap = cid_;
     u_.pending = true;
@@ -302,6 +307,10 @@ const char *ske_strerror(int code) {
     case SKE_ETALLYEXISTS: return "ERR tally already exists";
     case SKE_ETALLYCAP: return "ERR tally capacity out of range";
     case SKE_ETALLYSPACE: return "ERR tally list does not fit the output";
+    case SKE_ESEENNOSET: return "ERR seen set does not exist";
+    case SKE_ESEENEXISTS: return "ERR seen set already exists";
+    case SKE_ESEENCAP: return "ERR seen set capacity out of range";
+    case SKE_ESEENCALLS: return "ERR seen set has run out of call numbers";
     default: return "ERR unknown";
     }
 }
@@ -361,6 +370,10 @@ int ske_open(int device, ske_ctx **out) {
         const unsigned long long l = strtoull(v, nullptr, 10);
         c->tally_lds_log2 = l < kTallyLdsMinLog2 ? kTallyLdsMinLog2 : l > kTallyLdsMaxLog2 ? kTallyLdsMaxLog2 : int(l);
     }
+    if (const char *v = getenv("SKE_SEEN_GRID")) {
+        const unsigned long long grid = strtoull(v, nullptr, 10);
+        c->seen_grid = int(grid < kSeenMaxGrid ? grid : kSeenMaxGrid);
+    }
     if (hipMalloc(&c->zero16, 64) != hipSuccess || hipMemset(c->zero16, 0, 64) != hipSuccess) {
         ske_close(c);
         return SKE_ENOMEM;
@@ -378,6 +391,7 @@ int ske_close(ske_ctx *c) {
     for (auto &H : c->hh) free_hh(H);
     for (auto &P : c->tp) free_tp(P);
     for (auto &Y : c->tally) free_tally(Y);
+    for (auto &S : c->seen) free_seen(S);
     if (c->regs) (void)hipFree(c->regs);
     if (c->tau) (void)hipFree(c->tau);
     if (c->sig) (void)hipFree(c->sig);
@@ -388,6 +402,7 @@ int ske_close(ske_ctx *c) {
     if (c->zero16) (void)hipFree(c->zero16);
     if (c->xr.done) (void)hipEventDestroy(c->xr.done);
     if (c->rt.done) (void)hipEventDestroy(c->rt.done);
+    if (c->sn.done) (void)hipEventDestroy(c->sn.done);
     for (auto &m : c->marks) {
         if (m.own_a) (void)hipEventDestroy(m.a);
         (void)hipEventDestroy(m.b);
@@ -414,7 +429,7 @@ int ske_set_stream(ske_ctx *c, void *stream) {
     hipStream_t next = stream ? (hipStream_t)stream : c->own;
     // leaving the stream of the last scratch use: cover it now, while the
     // stream is known to be alive
-    for (ScratchUse *u : {&c->xr, &c->rt})
+    for (ScratchUse *u : {&c->xr, &c->rt, &c->sn})
         if (next != c->st && u->pending && u->stream == c->st) {
             bool covered = false;
             const int rc = xr_flush(c, *u, &covered);
@@ -594,7 +609,7 @@ int ske_capture_end(ske_ctx *c, void **graph_out) {
 int ske_graph_launch(ske_ctx *c, void *graph) {
     if (!c || !graph) return SKE_EINVAL;
     // a direct scratch use on another stream before the replay
-    for (ScratchUse *u : {&c->xr, &c->rt})
+    for (ScratchUse *u : {&c->xr, &c->rt, &c->sn})
         if (u->done && u->stream && u->stream != c->st && u->cap == 0) {
             bool covered = false;
             const int rc = xr_flush(c, *u, &covered);
@@ -608,9 +623,9 @@ int ske_graph_launch(ske_ctx *c, void *graph) {
     // both).  Two replays of graphs holding scratch users on different
     // streams are not ordered by this; replay such graphs on one stream.
     const auto gu = c->graph_users.find(graph);
-    const unsigned users = gu == c->graph_users.end() ? 3u : gu->second;
-    for (ScratchUse *u : {&c->xr, &c->rt})
-        if (u->done && (users & (u == &c->rt ? 2u : 1u))) {
+    const unsigned users = gu == c->graph_users.end() ? 7u : gu->second;
+    for (ScratchUse *u : {&c->xr, &c->rt, &c->sn})
+        if (u->done && (users & scratch_use_bit(c, u))) {
             HIPCHK(c, hipEventRecord(u->done, c->st));
             u->stream = c->st;
             u->cap = 0;

@@ -159,6 +159,40 @@ SKE_HD uint64_t murmur_short(uint64_t w, uint32_t len, uint64_t seed) {
     return mm_final(h);
 }
 
+// Seen-row sets (sketch_seen.hip): a row key is two 64-bit words.  It starts at
+// the two seeds; folding a column replaces each word k by MurmurHash64A(the
+// column's bytes, seed = k), so the key is a function of the columns' bytes,
+// their lengths and their order.  The set reads a word 0 (the empty slot) as 1.
+// A row's probe path starts at the low bits of its first word.
+constexpr uint64_t kSeenSeed0 = 0x9e3779b97f4a7c15ULL;
+constexpr uint64_t kSeenSeed1 = 0xd1b54a32d192ed03ULL;
+constexpr uint32_t kSeenMaxProbes = 128;  // slots one walk looks at (SKE_SEEN_MAX_PROBES)
+constexpr uint32_t kSeenLoadDen = 2;      // new claims stop at capacity / kSeenLoadDen (SKE_SEEN_LOAD_DEN)
+struct SeenKey {
+    uint64_t k0, k1;
+};
+SKE_HD SeenKey seen_begin() { return SeenKey{kSeenSeed0, kSeenSeed1}; }
+// one column of at most 16 bytes from its two zero-padded words
+SKE_HD SeenKey seen_fold_words(SeenKey k, uint64_t w0, uint64_t w1, uint32_t len) {
+    return SeenKey{murmur_words(w0, w1, len, k.k0), murmur_words(w0, w1, len, k.k1)};
+}
+// floor(epoch / granularity), granularity >= 1, also for a negative epoch
+SKE_HD int64_t seen_bucket(int64_t epoch, int64_t granularity) {
+    int64_t q = epoch / granularity;  // toward zero
+    if (epoch % granularity < 0) q -= 1;
+    return q;
+}
+// the time column: the bucket's 8 little-endian bytes
+SKE_HD SeenKey seen_fold_epoch(SeenKey k, int64_t epoch, int64_t granularity) {
+    const uint64_t b = uint64_t(seen_bucket(epoch, granularity));
+    return SeenKey{murmur_short(b, 8, k.k0), murmur_short(b, 8, k.k1)};
+}
+SKE_HD uint64_t seen_word(uint64_t k) { return k ? k : 1; }
+SKE_HD uint32_t seen_start(uint64_t k0, uint32_t capacity_log2) {
+    return uint32_t(k0 & ((uint64_t(1) << capacity_log2) - 1));
+}
+SKE_HD uint64_t seen_limit(uint32_t capacity_log2) { return (uint64_t(1) << capacity_log2) / kSeenLoadDen; }
+
 // ---------------------------------------------------------------------------
 // MurmurHash2, the 32-bit form (RedisBloom deps/murmur2/MurmurHash2.c
 // MurmurHash2): the Count-Min Sketch's row hash, cell of row i =

@@ -12,6 +12,7 @@
 //   sketch_api_hh.cpp      heavy-hitter sets beside a table: init, track, list, stats, select
 //   sketch_api_tp.cpp      time profiles (weekday x hour counters): init, add, read / import
 //   sketch_api_tally.cpp   tallies (exact event counts per key): init, add, query, list, top, import
+//   sketch_api_seen.cpp    seen-row sets (exact sets of 128-bit row keys): init, the folds, add, test
 // A helper used by one unit is static there; what crosses units is declared here.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -78,6 +79,18 @@ struct Tally {
     uint32_t log2 = 0;
 };
 
+// one seen-row set (base == nullptr: the sid is free); one allocation: a 64-byte
+// head (SeenHead), then the w0 words, the w1 words and the stamps
+struct Seen {
+    uint8_t *base = nullptr;
+    size_t bytes = 0;
+    uint32_t log2 = 0;
+    // the call counter as the host knows it: the device's at the last ske_seen_info
+    // plus the adds enqueued since (a graph's replays are not counted here; the
+    // kernels stop the counter themselves)
+    uint64_t calls_host = 0;
+};
+
 struct Staged {
     const uint8_t *bytes = nullptr;
     const uint32_t *offs = nullptr;
@@ -125,6 +138,10 @@ struct ske_ctx {
     int tally_form = 0;
     int tally_grid = 0;
     int tally_lds_log2 = ske::kTallyLdsMaxLog2;
+    std::vector<ske::Seen> seen;  // by sid (sized on first use)
+    // workgroups of the seen sets' kernels (SKE_SEEN_GRID, read by ske_open; 0:
+    // eight per CU); for small-shape tests, changes no result
+    int seen_grid = 0;
     // workgroups of ske_ingest_times / ske_ingest_dense (SKE_INGEST_GRID, read by
     // ske_open; 0: the ingest kernels' launch shape); for small-shape tests, changes no result
     int ingest_grid = 0;
@@ -153,12 +170,13 @@ struct ske_ctx {
     // previous one of its group (ScratchSlot's ordering rule, sketch_internal.h)
     ske::ScratchUse xr;  // K1's slots (kScrXr, kScrPart*, kScrSeg*)
     ske::ScratchUse rt;  // routing's slots (kScrRoute*): ordered among routing calls, not behind K1
+    ske::ScratchUse sn;  // the seen sets' slot (kScrSeenSlot): ordered among seen adds alone
     // executable graphs alive (recorded, not yet freed): they hold pointers to
     // the scratch and the register slab, so neither may be reallocated
     int live_graphs = 0;
     bool capturing = false;
     // scratch users recorded into the graph being captured (bit 0: xr,
-    // bit 1: rt), and per live graph the users its replays hold: a replay
+    // bit 1: rt, bit 2: sn), and per live graph the users its replays hold: a replay
     // records only their events, so a graph without routing does not order
     // the next routing call behind itself
     unsigned cap_users = 0;
@@ -237,7 +255,7 @@ private:
     bool open_ = false;  // begun, end event not yet recorded
 };
 
-// One use of an ordering group of the context scratch (c->xr or c->rt) by what
+// One use of an ordering group of the context scratch (c->xr, c->rt or c->sn) by what
 // is enqueued on `st` while the guard lives: the constructor makes st wait for
 // the group's last use on another stream (rc != 0: it failed, nothing may be
 // launched), the destructor notes this use on every exit after that.
@@ -289,6 +307,9 @@ void free_tp(Tp &P);
 
 // ---- sketch_api_tally.cpp
 void free_tally(Tally &Y);
+
+// ---- sketch_api_seen.cpp
+void free_seen(Seen &S);
 
 // ---- sketch_api_swipes.cpp
 bool use_lds(const ske_ctx *c, const ChainDev &ch);

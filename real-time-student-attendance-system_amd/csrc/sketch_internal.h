@@ -371,6 +371,48 @@ hipError_t launch_tally_list(const TallyTab &T, uint64_t min_events, uint32_t ca
 hipError_t launch_tally_head_add(const TallyTab &T, unsigned long long dropped_events,
                                  unsigned long long dropped_valid, uint32_t overflow, hipStream_t st);
 
+// sketch_seen.hip -- seen-row sets: an exact insert-only set of 128-bit row keys
+// whose add answers, per item, first sighting or repeat (DESIGN.md "Seen rows")
+constexpr uint8_t kSeenFirst = 0, kSeenRepeat = 1, kSeenSkipped = 2;  // SKE_SEEN_*
+constexpr uint32_t kSeenNoSlot = 0xffffffffu;    // per-item scratch: the walk found no slot
+constexpr uint32_t kSeenSkipSlot = 0xfffffffeu;  //   the mask kept the item out
+constexpr uint32_t kSeenLastCall = 0xfffffffeu;  // the call counter stops here: stamps stay below all ones
+constexpr unsigned kSeenMaxGrid = 4096;
+struct SeenHead {  // the first bytes of a set's allocation
+    unsigned int used;            // slots claimed
+    unsigned int pad_;
+    unsigned long long calls;     // adds run so far: the number of the next one
+    unsigned long long looked_at; // items the masks let through
+    unsigned long long first;     // of those, answered first (the unplaced ones included)
+    unsigned long long unplaced;  // of those, the ones that found no slot
+};
+struct SeenTab {
+    SeenHead *head;
+    unsigned long long *w0, *w1;  // per slot: the key's two words, 0 = not yet claimed
+    unsigned long long *stamp;    // per slot: (call << 32) | item of the first sighting, all ones = none
+    uint32_t mask;                // capacity - 1
+    uint32_t limit;               // capacity / kSeenLoadDen
+};
+// where a fold's column is: kind 0 packed, 1 fixed width, 2 spans (item i is
+// bytes[start[j] .. start[j] + len[j]), j = at ? at[i] : i), 3 epochs
+struct SeenCol {
+    int kind;
+    const uint8_t *bytes;
+    const uint32_t *offs;   // kind 0: offsets; kind 2: starts
+    const uint32_t *len;    // kind 2
+    const uint32_t *at;     // kind 2, may be null
+    const int64_t *epoch;   // kind 3
+    int64_t granularity;    // kind 3
+    uint32_t fixed_w, n;
+};
+// keys[2i], keys[2i + 1] = fold(begin ? the seeds : the words there, column item i)
+hipError_t launch_seen_fold(uint64_t *keys, const SeenCol &C, bool begin, unsigned grid, int cus, hipStream_t st);
+// the walk and the stamps, the answers, then the call counter's bump; slot: n words of scratch
+hipError_t launch_seen_add(const SeenTab &T, const uint64_t *keys, uint32_t n, const uint8_t *mask, uint32_t want,
+                           uint32_t *slot, uint8_t *out, unsigned grid, int cus, hipStream_t st);
+hipError_t launch_seen_test(const SeenTab &T, const uint64_t *keys, uint32_t n, uint8_t *present, unsigned grid,
+                            int cus, hipStream_t st);
+
 // sketch_hll_fmt.hip -- HLL keys as Redis "HYLL" strings, one key per workgroup
 // (DESIGN.md section 14); the opcode rules are sketch_hll_fmt.h's
 // sizes[i] = length of key i's string (slots == nullptr: keys 0 .. nkeys - 1);
@@ -393,7 +435,7 @@ hipError_t launch_hll_fmt_offs_check(const uint32_t *offs, uint32_t n, unsigned 
 
 // sketch_order.hip -- order-exact paths (replies that depend on item order)
 struct Scratch;  // growable device scratch, owned by the context
-constexpr int kScratchSlots = 52;
+constexpr int kScratchSlots = 56;
 
 // Every slot of the context scratch, by owner (who sizes it) and user.  The
 // numbers carry no meaning beyond identity; a slot belongs to exactly one of
@@ -401,7 +443,8 @@ constexpr int kScratchSlots = 52;
 //   sync  used only inside synchronous calls, which run on the context stream
 //         and end with a stream synchronise, so two such calls never overlap;
 //   xr    K1's per-launch state, ordered through ske_ctx::xr (ScratchUser);
-//   rt    routing's, ordered through ske_ctx::rt.
+//   rt    routing's, ordered through ske_ctx::rt;
+//   sn    the seen sets' per-item slots, ordered through ske_ctx::sn.
 // The rule: a slot reachable from an rt-ordered call may have no user ordered
 // through xr, and the other way round -- routing runs beside K1 on another
 // stream (distributed.SwipeExchange's pipelined form), and neither waits for
@@ -464,6 +507,8 @@ enum ScratchSlot : int {
     // -- rt
     kScrRouteHist,     // ske_route_swipes, ske_route_swipes_cap_async: per-block histogram,
     kScrRouteTot,      // ske_route_swipes: the owners' totals
+    // -- sn
+    kScrSeenSlot,      // ske_seen_add_async: the slot each item's walk ended at, from the walk to the answers
     kScratchSlotCount
 };
 static_assert(kScratchSlotCount <= kScratchSlots, "Scratch holds kScratchSlots slots");
@@ -498,6 +543,9 @@ enum StageSlot : int {
     kStgTallyLen,      //   lengths,
     kStgTallyEv,       //   events (also ske_tally_query's reply on its way to the host),
     kStgTallyVa,       //   valid (likewise)
+    kStgSeenKeys,      // ske_seen_add / ske_seen_test: the keys,
+    kStgSeenMask,      //   ske_seen_add: a mask byte per item,
+    kStgSeenOut,       //   the answers on their way to the host
     kStageSlotCount
 };
 

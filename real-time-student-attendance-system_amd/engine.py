@@ -14,7 +14,7 @@ import gc
 import numpy as np
 
 from ._lib import (CmsInfo, Context, GenParams, HhInfo, HhStats, IngestDense, SKE_HH_ID_BYTES, SKE_HLL_DUMP_CARD,
-                   SKE_MEM_DEVICE, SKE_MEM_HOST, SKE_TALLY_KEY_BYTES, SKE_TP_BINS, TallyInfo)
+                   SKE_MEM_DEVICE, SKE_MEM_HOST, SKE_TALLY_KEY_BYTES, SKE_TP_BINS, SeenInfo, TallyInfo)
 from . import synthetic
 
 PASS_KINDS = 9  # SKE_PASS_KINDS (include/sketch.h)
@@ -205,6 +205,42 @@ def tally_import(ctx: Context, tid: int, keys, events, valid) -> None:
     va = np.ascontiguousarray(valid, dtype=np.uint64)
     ctx.call("ske_tally_import", int(tid), kb.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
              ev.ctypes.data_as(C.c_void_p), va.ctypes.data_as(C.c_void_p), n)
+
+
+def seen_info(ctx: Context, sid: int) -> dict:
+    """ske_seen_info: capacity, limit, used, the adds run so far, the items
+    the masks let through, the first sightings among them and the items that
+    found no slot (answered first: the set fails open)."""
+    info = SeenInfo()
+    ctx.call("ske_seen_info", int(sid), C.byref(info))
+    return {k: int(getattr(info, k)) for k, _ in SeenInfo._fields_}
+
+
+def seen_add_keys(ctx: Context, sid: int, keys: np.ndarray, mask=None, want: int = 0) -> np.ndarray:
+    """ske_seen_add over a host ``[n, 2]`` uint64 array of row keys: one answer
+    byte per key (SKE_SEEN_FIRST / REPEAT / SKIPPED)."""
+    k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, 2)
+    n = k.shape[0]
+    out = np.zeros(n, np.uint8)
+    m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+    if m is not None and m.size != n:
+        raise ValueError("one mask byte per key")
+    if n:
+        ctx.call("ske_seen_add", int(sid), k.ctypes.data_as(C.c_void_p), n,
+                 None if m is None else m.ctypes.data_as(C.c_void_p), int(want), out.ctypes.data_as(C.c_void_p),
+                 SKE_MEM_HOST)
+    return out
+
+
+def seen_test_keys(ctx: Context, sid: int, keys: np.ndarray) -> np.ndarray:
+    """ske_seen_test over a host ``[n, 2]`` uint64 array: bool per key."""
+    k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, 2)
+    n = k.shape[0]
+    out = np.zeros(n, np.uint8)
+    if n:
+        ctx.call("ske_seen_test", int(sid), k.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p),
+                 SKE_MEM_HOST)
+    return out.astype(bool)
 
 
 class SweBatch(C.Structure):
@@ -572,6 +608,44 @@ class SketchEngine:
 
     def tally_import(self, tid: int, keys, events, valid):
         tally_import(self.ctx, tid, keys, events, valid)
+
+    # ---- seen-row sets (count each row once under redelivery)
+    def seen_init(self, sid: int, capacity_log2: int):
+        self.ctx.call("ske_seen_init", int(sid), int(capacity_log2))
+
+    def seen_free(self, sid: int):
+        self.ctx.call("ske_seen_free", int(sid))
+
+    def seen_reset(self, sid: int):
+        self.ctx.call("ske_seen_reset", int(sid))
+
+    def seen_info(self, sid: int) -> dict:
+        return seen_info(self.ctx, sid)
+
+    def seen_fold(self, keys: DeviceBuffer, b: DeviceBatch, begin: bool):
+        """One resident column folded into the ``2 * b.n`` key words of
+        ``keys`` (ske_seen_fold_fixed_async for a fixed-width batch, else
+        ske_seen_fold_packed_async; capturable)."""
+        if b.width:
+            self.ctx.call("ske_seen_fold_fixed_async", C.c_void_p(keys.ptr), C.c_void_p(b.bytes.ptr), b.width, b.n,
+                          1 if begin else 0)
+        else:
+            self.ctx.call("ske_seen_fold_packed_async", C.c_void_p(keys.ptr), C.c_void_p(b.bytes.ptr),
+                          C.c_void_p(b.offs.ptr), b.n, 1 if begin else 0)
+
+    def seen_fold_epoch(self, keys: DeviceBuffer, epoch: DeviceBuffer, n: int, granularity: int, begin: bool):
+        self.ctx.call("ske_seen_fold_epoch_async", C.c_void_p(keys.ptr), C.c_void_p(epoch.ptr), int(granularity),
+                      int(n), 1 if begin else 0)
+
+    def seen_add(self, sid: int, keys: DeviceBuffer, n: int, out: DeviceBuffer, mask: DeviceBuffer | None = None,
+                 want: int = 0):
+        """ske_seen_add_async: one answer byte per key into ``out`` (only
+        enqueued, capturable; ``sync()`` waits)."""
+        self.ctx.call("ske_seen_add_async", int(sid), C.c_void_p(keys.ptr), int(n),
+                      C.c_void_p(mask.ptr) if mask is not None else None, int(want), C.c_void_p(out.ptr))
+
+    def seen_test(self, sid: int, keys: DeviceBuffer, n: int, out: DeviceBuffer):
+        self.ctx.call("ske_seen_test_async", int(sid), C.c_void_p(keys.ptr), int(n), C.c_void_p(out.ptr))
 
     # ---- ingest: the decoded messages' times, and the decoded messages as one packed batch
     def ingest_times(self, msgs: DeviceBuffer, cols, n: int, epoch: DeviceBuffer):

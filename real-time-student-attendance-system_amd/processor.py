@@ -115,9 +115,11 @@ class AttendanceProcessor:
             self.acked += len(rows)
             if self.counts is not None:  # the rows the reference inserts, invalid ones included
                 buf, offs = pack(ids)
-                lectured = getattr(self.counts, "counts_lectures", False)
+                # what the counting call asks for: a profile / tally that exists, or the row keys of dedup
+                timed = getattr(self.counts, "needs_times", self.counts.timed)
+                lectured = getattr(self.counts, "needs_lectures", getattr(self.counts, "counts_lectures", False))
                 self.counts.count_packed(buf, offs, valid,
-                                         [r["timestamp"] for r in rows] if self.counts.timed else None,
+                                         [r["timestamp"] for r in rows] if timed else None,
                                          **({"lectures": [r["lecture_id"] for r in rows]} if lectured else {}))
         return rows
 
@@ -182,7 +184,10 @@ class AttendanceProcessor:
         prefix of another, e.g. 'A' and 'A:B', keeps its own keys).  When
         ``counts`` has a lecture tally the dict also carries
         ``attendance_record_count`` and ``invalid_record_count``, the lecture's
-        rows valid or not and the invalid ones, over every day."""
+        rows valid or not and the invalid ones, over every day.  When ``counts``
+        keeps a seen-row set (``dedup``) those are distinct rows, and
+        ``duplicate_record_count`` is how many redelivered rows, of any
+        lecture, the set kept out of the counts."""
         out = {"unique_attendees": self._unique_attendees(lecture_id, day)}
         if getattr(self.counts, "counts_lectures", False):
             # the reference's attendance_records (:154-165), rows per lecture over
@@ -190,6 +195,8 @@ class AttendanceProcessor:
             ev, va = self.counts.lecture_events([lecture_id])
             out["attendance_record_count"] = int(ev[0])
             out["invalid_record_count"] = int(ev[0]) - int(va[0])
+        if getattr(self.counts, "dedup", False):
+            out["duplicate_record_count"] = self.counts.duplicate_rows()
         return out
 
     def _unique_attendees(self, lecture_id: str, day: str | None) -> int:
