@@ -31,7 +31,8 @@
  *     caller-chosen `cid` < SKE_MAX_CMS, heavy-hitter sets by a caller-chosen
  *     `hid` < SKE_MAX_HH, time profiles by a caller-chosen `tid` < SKE_MAX_TP,
  *     tallies by a caller-chosen `tid` < SKE_MAX_TALLY, seen-row sets by a
- *     caller-chosen `sid` < SKE_MAX_SEEN (spaces of their own).
+ *     caller-chosen `sid` < SKE_MAX_SEEN, row logs by a caller-chosen `rid` <
+ *     SKE_MAX_ROWS (spaces of their own).
  *     The facade maps Redis key names to fids / slots /
  *     cids.
  */
@@ -87,6 +88,12 @@ extern "C" {
 #define SKE_ESEENCAP -39     /* capacity_log2 outside [SKE_SEEN_MIN_LOG2, SKE_SEEN_MAX_LOG2] */
 #define SKE_ESEENCALLS -40   /* the set's 32-bit call counter would wrap: ske_seen_reset starts it again */
 
+/* -41 is not assigned */
+#define SKE_EROWSNOLOG -42   /* row log id not in use */
+#define SKE_EROWSEXISTS -43  /* ske_rows_init on an id in use */
+#define SKE_EROWSCAP -44     /* capacity_log2 outside [SKE_ROWS_MIN_LOG2, SKE_ROWS_MAX_LOG2] */
+#define SKE_EROWSSPACE -45   /* ske_rows_select: more rows pass than the output arrays hold */
+
 #define SKE_MEM_HOST 0
 #define SKE_MEM_DEVICE 1
 
@@ -120,6 +127,11 @@ extern "C" {
 #define SKE_SEEN_FIRST 0       /* ske_seen_add's answer bytes: count this row, */
 #define SKE_SEEN_REPEAT 1      /*   a repeat, */
 #define SKE_SEEN_SKIPPED 2     /*   the mask kept the item out */
+#define SKE_MAX_ROWS 8
+#define SKE_ROWS_MIN_LOG2 8
+#define SKE_ROWS_MAX_LOG2 28   /* a position fits a u32 */
+#define SKE_ROWS_BLOCK 256     /* items per workgroup and tile of an append: positions are tile prefix + rank */
+#define SKE_ROWS_ROW_BYTES 25  /* lec 8, epoch 8, id 8, valid 1 */
 #define SKE_HLL_REGISTERS 16384
 #define SKE_HLL_DENSE_BYTES 12288
 #define SKE_HLL_DUMP_MAX_KEYS (1u << 18)   /* 2^18 * 12304 B < 2^32: u32 offsets suffice */
@@ -718,6 +730,100 @@ int ske_seen_add(ske_ctx *ctx, uint32_t sid, const uint64_t *keys, uint64_t n, c
                  uint8_t *out, int mem);
 int ske_seen_test(ske_ctx *ctx, uint32_t sid, const uint64_t *keys, uint64_t n, uint8_t *present_out, int mem);
 
+/* ---- row logs: the attendance rows themselves, in arrival order ----
+ * The counterpart of the reference's Cassandra table (attendance_processor.py:
+ * 64-72 the schema, :134-136 the insert, :154-165 the per-lecture read;
+ * attendance_analysis.py:19-52 the whole-table read): a device-resident,
+ * append-only log of (lecture, timestamp, student_id, is_valid) in four columns
+ * of 2^capacity_log2 entries, SKE_ROWS_ROW_BYTES a row, addressed by a
+ * caller-chosen rid < SKE_MAX_ROWS; the context owns it.
+ *   lec    u64  the lecture's digest: MurmurHash64A of the lecture bytes (any
+ *               length), the Bloom seed, 0 mapped to 1 -- a tally's identity rule,
+ *               so a tally listing names the log's partitions.  Two lectures with
+ *               equal digests are one partition (the tally's limit).
+ *   epoch  i64  seconds since 1970-01-01T00:00:00 UTC
+ *   id     i64  the student id as an integer (the table's `student_id int`)
+ *   valid  u8   is_valid, 0 or 1
+ * A row's position is its arrival sequence number; nothing else orders rows.
+ *
+ * Append.  Row i is taken when status_or_null is NULL or status[i] == 0 and
+ * mask_or_null is NULL or mask[i] == 1.  Its id must be an integer:
+ *   packed, spans: canonical decimal text -- "-"? then digits, no leading zero
+ *     except "0" itself, no "-0", no "+", no blanks, fitting int64.  Anything
+ *     else is not a Cassandra int: the row is refused and counted (refused_ids),
+ *     there is no error path.
+ *   fixed: `width` bytes at ids + i * width; 8 a little-endian int64, 4 a
+ *     little-endian int32, sign-extended; other widths SKE_EINVAL.
+ * The taken rows with an integer id land at used + (their rank among such rows
+ * of the batch): a stable compaction, so the log's contents and layout are the
+ * same from run to run and position order is arrival order within and across
+ * calls.  Rows that do not fit are dropped from the batch's tail (the prefix
+ * that fits is kept, in order), counted in `dropped`, and set the sticky
+ * `overflow`.  Always used + refused_ids + dropped == taken.  valid_dev_or_null
+ * NULL stores 0 (as a missing Bloom key answers).  The head lives in the log
+ * and is advanced by the call's own last kernel, so a recorded append appends
+ * again at every replay.  Enqueue only and graph-capturable; n < 2^32 - 1.  The
+ * per-item state between the call's kernels is context scratch: record the
+ * call after one direct call of at least its size.
+ *   packed: lecture i = lec_bytes[lec_offs[i] .. lec_offs[i + 1]), id likewise;
+ *   spans: lecture i = bytes[lec_start[i] .. lec_start[i] + lec_len[i]), id
+ *     likewise -- the columns of ske_ingest_parse read in place, with its status;
+ *     only the aligned 8-byte words that hold a byte of an item are read, and no
+ *     span of a row that is not taken is looked at;
+ *   fixed: lectures packed, ids fixed width.
+ *
+ * Select.  The rows of one lecture (lec_bytes_or_null NULL: of every lecture)
+ * with since <= epoch < until (INT64_MIN / INT64_MAX leave that end open), in
+ * the table's order: (epoch, id) ascending, both signed, and with no lecture
+ * given the digest, compared unsigned, in front (Cassandra orders partitions
+ * by token, which is arbitrary; digest order is the counterpart).  Each run of
+ * equal (lec, epoch, id) collapses to its last-appended row -- the table's
+ * upsert: a redelivered row overwrites itself, is_valid included.  *n_out = the
+ * rows after the collapse, *complete = 0 once the log's overflow is set; both
+ * are always written.  More than cap: SKE_EROWSSPACE with no output array
+ * touched, so cap = 0 (every output pointer may be NULL then) is the count; it
+ * succeeds when *n_out is 0.  mem says where the four output arrays are.
+ * Waits for the stream: SKE_EBUSY while a capture records. */
+typedef struct {
+    uint64_t capacity;     /* rows it holds */
+    uint64_t used;         /* rows held: the next row's position */
+    uint64_t taken;        /* rows the statuses and masks let through */
+    uint64_t refused_ids;  /* of those, the ones whose id is not an integer */
+    uint64_t dropped;      /* of those, the ones that found the log full */
+    uint64_t overflow;     /* sticky: a row was dropped */
+} ske_rows_info_t;
+/* empty; SKE_EROWSEXISTS when rid is in use, SKE_EROWSCAP for a capacity out of range */
+int ske_rows_init(ske_ctx *ctx, uint32_t rid, uint32_t capacity_log2);
+/* SKE_EBUSY while a recorded graph is alive or being recorded */
+int ske_rows_free(ske_ctx *ctx, uint32_t rid);
+/* an empty log again, its counts zeroed */
+int ske_rows_reset(ske_ctx *ctx, uint32_t rid);
+int ske_rows_info(ske_ctx *ctx, uint32_t rid, ske_rows_info_t *out);
+int ske_rows_append_packed_async(ske_ctx *ctx, uint32_t rid, const uint8_t *lec_bytes_dev,
+                                 const uint32_t *lec_offs_dev, const uint8_t *id_bytes_dev,
+                                 const uint32_t *id_offs_dev, const int64_t *epoch_dev,
+                                 const uint8_t *valid_dev_or_null, const uint8_t *mask_or_null, uint64_t n);
+int ske_rows_append_spans_async(ske_ctx *ctx, uint32_t rid, const uint8_t *bytes_dev, const uint32_t *lec_start_dev,
+                                const uint32_t *lec_len_dev, const uint32_t *id_start_dev,
+                                const uint32_t *id_len_dev, const uint8_t *status_or_null, const int64_t *epoch_dev,
+                                const uint8_t *valid_dev_or_null, const uint8_t *mask_or_null, uint64_t n);
+int ske_rows_append_fixed_async(ske_ctx *ctx, uint32_t rid, const uint8_t *lec_bytes_dev,
+                                const uint32_t *lec_offs_dev, const uint8_t *ids_dev, uint32_t width,
+                                const int64_t *epoch_dev, const uint8_t *valid_dev_or_null,
+                                const uint8_t *mask_or_null, uint64_t n);
+/* The packed form over host or device arrays (mem covers every input); returns
+ * when done.  Appending what ske_rows_read returned, ids as text, restores a log. */
+int ske_rows_append(ske_ctx *ctx, uint32_t rid, const uint8_t *lec_bytes, const uint32_t *lec_offs,
+                    const uint8_t *id_bytes, const uint32_t *id_offs, const int64_t *epoch,
+                    const uint8_t *valid_or_null, const uint8_t *mask_or_null, uint64_t n, int mem);
+int ske_rows_select(ske_ctx *ctx, uint32_t rid, const uint8_t *lec_bytes_or_null, uint32_t lec_len, int64_t since,
+                    int64_t until, uint64_t *out_lec, int64_t *out_epoch, int64_t *out_id, uint8_t *out_valid,
+                    uint64_t cap, uint64_t *n_out, int *complete, int mem);
+/* The raw columns of positions [first, first + n) to host arrays (a checkpoint);
+ * SKE_EINVAL when first + n passes `used`. */
+int ske_rows_read(ske_ctx *ctx, uint32_t rid, uint64_t first, uint64_t n, uint64_t *out_lec, int64_t *out_epoch,
+                  int64_t *out_id, uint8_t *out_valid);
+
 /* ---- the fused hot path (K1) ----
  * For every swipe i: v = BF.EXISTS fid id_i; if v: PFADD slot_i id_i.
  *   replaces the per-event pair attendance_processor.py:109-113 + :127-129.
@@ -935,6 +1041,7 @@ int ske_ingest_dense(ske_ctx *ctx, const uint8_t *msgs, const ske_ingest_cols_t 
  * ske_tally_add_packed_async, ske_tally_add_fixed_async, ske_tally_add_spans_async,
  * ske_seen_fold_packed_async, ske_seen_fold_fixed_async, ske_seen_fold_spans_async,
  * ske_seen_fold_epoch_async, ske_seen_add_async, ske_seen_test_async,
+ * ske_rows_append_packed_async, ske_rows_append_spans_async, ske_rows_append_fixed_async,
  * ske_ingest_times) into an executable graph, uploaded to the device;
  * each ske_graph_launch replays it on the context stream.  A consumer that
  * processes a ring of fixed device batch slots replays one graph per turn of

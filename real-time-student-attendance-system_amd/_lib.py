@@ -53,6 +53,10 @@ SKE_ESEENNOSET = -37
 SKE_ESEENEXISTS = -38
 SKE_ESEENCAP = -39
 SKE_ESEENCALLS = -40
+SKE_EROWSNOLOG = -42
+SKE_EROWSEXISTS = -43
+SKE_EROWSCAP = -44
+SKE_EROWSSPACE = -45
 SKE_MEM_HOST = 0
 SKE_MEM_DEVICE = 1
 SKE_MAX_FILTERS = 4096
@@ -82,6 +86,11 @@ SKE_SEEN_LOAD_DEN = 2
 SKE_SEEN_FIRST = 0
 SKE_SEEN_REPEAT = 1
 SKE_SEEN_SKIPPED = 2
+SKE_MAX_ROWS = 8
+SKE_ROWS_MIN_LOG2 = 8
+SKE_ROWS_MAX_LOG2 = 28
+SKE_ROWS_BLOCK = 256
+SKE_ROWS_ROW_BYTES = 25
 HLL_REGISTERS = 16384
 HLL_DENSE_BYTES = 12288
 SKE_HLL_DUMP_MAX_KEYS = 1 << 18
@@ -133,6 +142,12 @@ class SeenInfo(C.Structure):
     """ske_seen_info_t (include/sketch.h)."""
     _fields_ = [("capacity", C.c_uint64), ("limit", C.c_uint64), ("used", C.c_uint64), ("calls", C.c_uint64),
                 ("looked_at", C.c_uint64), ("first", C.c_uint64), ("unplaced", C.c_uint64)]
+
+
+class RowsInfo(C.Structure):
+    """ske_rows_info_t (include/sketch.h)."""
+    _fields_ = [("capacity", C.c_uint64), ("used", C.c_uint64), ("taken", C.c_uint64),
+                ("refused_ids", C.c_uint64), ("dropped", C.c_uint64), ("overflow", C.c_uint64)]
 
 
 class IngestCols(C.Structure):
@@ -270,6 +285,21 @@ SIGNATURES = {
     "ske_seen_test_async": (C.c_int, [_CTX, C.c_uint32, _u64p, C.c_uint64, _u8p]),
     "ske_seen_add": (C.c_int, [_CTX, C.c_uint32, _u64p, C.c_uint64, _u8p, C.c_int, _u8p, C.c_int]),
     "ske_seen_test": (C.c_int, [_CTX, C.c_uint32, _u64p, C.c_uint64, _u8p, C.c_int]),
+    "ske_rows_init": (C.c_int, [_CTX, C.c_uint32, C.c_uint32]),
+    "ske_rows_free": (C.c_int, [_CTX, C.c_uint32]),
+    "ske_rows_reset": (C.c_int, [_CTX, C.c_uint32]),
+    "ske_rows_info": (C.c_int, [_CTX, C.c_uint32, C.POINTER(RowsInfo)]),
+    "ske_rows_append_packed_async": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, _u8p, _u32p, _vp, _u8p, _u8p,
+                                               C.c_uint64]),
+    "ske_rows_append_spans_async": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, _u32p, _u32p, _u32p, _u8p, _vp, _u8p,
+                                              _u8p, C.c_uint64]),
+    "ske_rows_append_fixed_async": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, _u8p, C.c_uint32, _vp, _u8p, _u8p,
+                                              C.c_uint64]),
+    "ske_rows_append": (C.c_int, [_CTX, C.c_uint32, _u8p, _u32p, _u8p, _u32p, _vp, _u8p, _u8p, C.c_uint64,
+                                  C.c_int]),
+    "ske_rows_select": (C.c_int, [_CTX, C.c_uint32, _u8p, C.c_uint32, C.c_int64, C.c_int64, _u64p, _vp, _vp, _u8p,
+                                  C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_int]),
+    "ske_rows_read": (C.c_int, [_CTX, C.c_uint32, C.c_uint64, C.c_uint64, _u64p, _vp, _vp, _u8p]),
     "ske_swipes": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p, C.c_int]),
     "ske_swipes_async": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p]),
     "ske_swipes_fixed": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, C.c_uint32, C.c_uint64, _u8p,

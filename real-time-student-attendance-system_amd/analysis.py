@@ -34,6 +34,12 @@ gives some rows twice.  With ``dedup`` set, a seen-row set (client_seen.py,
 DESIGN.md "Seen rows") answers per row whether it was counted before, and only
 first sightings reach the counters -- the reference's analytics read a
 Cassandra table in which a redelivered row overwrites itself.
+
+That table's rows have a counterpart too.  With ``records`` set, a row log
+(client_rows.py, DESIGN.md "Row log") keeps every row the counting calls are
+given -- (lecture, time, student id, is_valid), in arrival order, on the
+device -- and ``records`` reads a lecture's rows back in the table's order,
+each row once with its last write.
 """
 from __future__ import annotations
 
@@ -155,15 +161,28 @@ class StudentCounts:
     still runs on every row and the returned validity is unchanged.  With it
     set the counting calls need the swipes' times and lectures whether or not
     the time and lecture options are on (``needs_times`` / ``needs_lectures``).
-    A set that is full answers "first": a count is never lost."""
+    A set that is full answers "first": a count is never lost.
+
+    ``records`` (default None: off): the name of a row log
+    (``client.rows_create``; made here with ``2 ** records_capacity_log2`` rows
+    when it does not exist), the counterpart of the reference's Cassandra
+    table.  ``update``, ``count_packed`` and ``update_messages`` then append
+    every row they are given -- every acknowledged row, valid or not, before any
+    ``dedup`` compaction; the log collapses repeats itself when it is read
+    (``records``).  The id must be an integer: ``update`` takes 4- or 8-byte
+    little-endian ids only, the other calls the id's canonical decimal text;
+    anything else is refused and counted (``records_info()["refused_ids"]``).
+    With it set the counting calls need the swipes' times and lectures."""
 
     def __init__(self, client, attended_key="cms:attended", invalid_key="cms:invalid",
                  error: float = 0.001, probability: float = 0.01, track_attended: int | None = None,
                  track_invalid: int | None = None, capacity_log2: int = 16, late_key=None,
                  late_from: int = 9 * 3600, track_late: int | None = None, day_profile=None,
                  lecture_counts=None, lecture_capacity_log2: int = 16, dedup=None,
-                 dedup_capacity_log2: int = 22, dedup_granularity: int = 1):
+                 dedup_capacity_log2: int = 22, dedup_granularity: int = 1, records=None,
+                 records_capacity_log2: int = 22):
         self.client = client
+        self._records = encode(records) if records is not None else None
         self._dedup = encode(dedup) if dedup is not None else None
         self._dedup_gran = int(dedup_granularity)
         if self._dedup_gran < 1:
@@ -210,6 +229,8 @@ class StudentCounts:
             client.tally_create(self._lectures, lecture_capacity_log2)
         if self._dedup is not None and self._dedup not in client._seen:
             client.seen_create(self._dedup, dedup_capacity_log2)
+        if self._records is not None and self._records not in client._rows:
+            client.rows_create(self._records, records_capacity_log2)
 
     def _buffers(self, n: int, width: int):
         b = self._bufs
@@ -280,12 +301,16 @@ class StudentCounts:
         if ids.ndim != 2:
             raise ValueError("ids must be a [n, width] uint8 array")
         n, width = ids.shape
+        if self._records is not None and width not in (4, 8):
+            raise ValueError("with records an id is a 4- or 8-byte little-endian integer")
         ep = self._check_times(times, n)
         lec = self._check_lectures(lectures, n)
         if n == 0 or width == 0:
             return np.zeros(n, bool)
         if self._dedup is not None:
             return self._update_dedup(bf_key, slots, ids, ep, lec)
+        rows = (ep, lec)  # the log's columns; the counters take theirs only where their option is on
+        ep, lec = ep if self.timed else None, lec if self.counts_lectures else None
         s = np.ascontiguousarray(slots, dtype=np.uint32)
         if s.shape != (n,):
             raise ValueError("one slot per id")
@@ -300,6 +325,8 @@ class StudentCounts:
                         width, n, C.c_void_p(d_valid.ptr), SKE_MEM_DEVICE)
         else:
             d_valid.from_host(np.zeros(n, np.uint8))  # BF.EXISTS of a missing key answers 0
+        if self._records is not None:  # every row, with K1's answers where they are
+            cl.rows_enqueue(cl.rows_rid(self._records), rows[1], rows[0], fixed_ids=ids, d_valid=d_valid)
         for key, want in ((self.attended_key, 1), (self.invalid_key, 0)):
             cl.ctx.call("ske_cms_add_fixed_async", cl.cms_cid(key), C.c_void_p(d_ids.ptr), width, n,
                         None, C.c_void_p(d_valid.ptr), want)
@@ -344,14 +371,37 @@ class StudentCounts:
     @property
     def needs_times(self) -> bool:
         """Whether the counting calls need the swipes' times: for a profile
-        (``timed``) or for the row keys of ``dedup``."""
-        return self._profile is not None or self._dedup is not None
+        (``timed``), for the row keys of ``dedup`` or for the rows of ``records``."""
+        return self._profile is not None or self._dedup is not None or self._records is not None
 
     @property
     def needs_lectures(self) -> bool:
         """Whether the counting calls need the swipes' lectures: for the tally
-        (``counts_lectures``) or for the row keys of ``dedup``."""
-        return self._lectures is not None or self._dedup is not None
+        (``counts_lectures``), for the row keys of ``dedup`` or for the rows of ``records``."""
+        return self._lectures is not None or self._dedup is not None or self._records is not None
+
+    @property
+    def keeps_records(self) -> bool:
+        """Whether a row log keeps every row (``records``)."""
+        return self._records is not None
+
+    def records(self, lecture=None, since=None, until=None) -> dict:
+        """``client.rows_select`` over the log: the rows of ``lecture`` (None:
+        every lecture's, digest-major) with ``since <= time < until`` (seconds,
+        or anything ``epoch_seconds`` takes; None: open), each (lecture, time,
+        id) once with its last write, in (time, id) order."""
+        if self._records is None:
+            raise ValueError("no records")
+        lo = None if since is None else int(epoch_seconds([since])[0])
+        hi = None if until is None else int(epoch_seconds([until])[0])
+        return self.client.rows_select(self._records, lecture, lo, hi)
+
+    def records_info(self) -> dict:
+        """``client.rows_info`` of the log: capacity, used, taken, refused_ids,
+        dropped, overflow."""
+        if self._records is None:
+            raise ValueError("no records")
+        return self.client.rows_info(self._records)
 
     def duplicate_rows(self) -> int:
         """Rows the seen set kept out of the counts so far: ``looked_at - first``."""
@@ -408,6 +458,8 @@ class StudentCounts:
             cl.ctx.call("ske_swipes_fixed", cl.keys.fid[bkey], C.c_void_p(d_slots.ptr), C.c_void_p(d_ids.ptr),
                         width, n, C.c_void_p(d_valid.ptr), SKE_MEM_DEVICE)
             valid = d_valid.to_host(np.uint8, n)
+        if self._records is not None:  # every row, before the repeats leave
+            cl.rows_enqueue(cl.rows_rid(self._records), lec, ep, fixed_ids=ids, valid=valid)
         offs = (np.arange(n + 1, dtype=np.uint64) * width).astype(np.uint32)
         self._count_first(ids.reshape(-1), offs, valid, ep, lec)
         return valid.astype(bool)
@@ -490,10 +542,12 @@ class StudentCounts:
         lec = self._check_lectures(lectures, n)
         if n == 0:
             return
+        if self._records is not None:  # every row, before the repeats leave
+            self.client.rows_enqueue(self.client.rows_rid(self._records), lec, ep, ids=(buf, offs), valid=v)
         if self._dedup is not None:
             self._count_first(buf, offs, v, ep, lec)
         else:
-            self._count_kept(buf, offs, v, ep, lec)
+            self._count_kept(buf, offs, v, ep if self.timed else None, lec if self.counts_lectures else None)
 
     def _count_kept(self, buf, offs, v, ep, lec) -> None:
         """``count_packed``'s work over checked arrays."""
@@ -540,6 +594,12 @@ class StudentCounts:
         if self.needs_times:
             cl.ctx.call("ske_ingest_times", msgs, C.byref(run.cols), n, C.c_void_p(d["epoch_all"].ptr))
         cols = run.cols
+        if self._records is not None:
+            # every decoded message's row from the parse columns in place: the parse's own status
+            # (not the seen set's answers), the message times and K1's valid bytes
+            cl.ctx.call("ske_rows_append_spans_async", cl.rows_rid(self._records), msgs, cols.lec_start,
+                        cols.lec_len, cols.id_start, cols.id_len, cols.status, C.c_void_p(d["epoch_all"].ptr),
+                        C.c_void_p(B["valid"].ptr) if run.has_bf else None, None, n)
         if self._dedup is not None:
             # The row keys from the parse columns in place, per message; the
             # set's answer bytes then stand in for the status column: 0 is a

@@ -37,8 +37,8 @@ The client is composed per native unit (csrc/sketch_api_*.cpp): the key table
 (keyspace.py), Bloom (client_bloom.py), Count-Min Sketch (client_cms.py),
 heavy-hitter sets beside a CMS key (client_hh.py), HLL (client_hll.py), the
 fused swipe path (client_swipes.py), the device ingest (client_ingest.py),
-the time profiles (client_tp.py), the tallies (client_tally.py) and the
-seen-row sets (client_seen.py);
+the time profiles (client_tp.py), the tallies (client_tally.py), the
+seen-row sets (client_seen.py) and the row logs (client_rows.py);
 commands.py holds the command table, ``bf()`` / ``cms()`` and the pipeline.  Here: the constructor, the generic key commands and
 ``execute_command``.
 """
@@ -50,6 +50,7 @@ from .client_cms import CmsMixin
 from .client_hh import HhMixin
 from .client_hll import HllMixin
 from .client_ingest import IngestMixin
+from .client_rows import RowsMixin
 from .client_seen import SeenMixin
 from .client_swipes import SwipesMixin
 from .client_tally import TallyMixin
@@ -63,7 +64,7 @@ from .keyspace import (BF_TYPE_NAME, CMS_TYPE_NAME, KIND_TYPE_NAMES, TYPE_NAME_K
 
 
 class SketchClient(BloomMixin, CmsMixin, HhMixin, HllMixin, SwipesMixin, IngestMixin, TimeProfileMixin,
-                   TallyMixin, SeenMixin):
+                   TallyMixin, SeenMixin, RowsMixin):
     """Drop-in for ``redis.Redis`` on the reference's Bloom + HLL calls."""
 
     def __init__(self, host: str = "localhost", port: int = 6379, db: int = 0,
@@ -78,6 +79,7 @@ class SketchClient(BloomMixin, CmsMixin, HhMixin, HllMixin, SwipesMixin, IngestM
         self._tp_init_registry()
         self._tally_init_registry()
         self._seen_init_registry()
+        self._rows_init_registry()
 
     # ------------------------------------------------------------ helpers
     def _ok(self):
@@ -135,6 +137,8 @@ class SketchClient(BloomMixin, CmsMixin, HhMixin, HllMixin, SwipesMixin, IngestM
             self._tally_release()
         if self._seen:
             self._seen_release()
+        if self._rows:
+            self._rows_release()
         for key in list(self.keys.kind):
             self.keys.drop(key)
         return True

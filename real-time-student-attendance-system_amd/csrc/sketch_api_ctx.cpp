@@ -1,7 +1,7 @@
 // sketch_api_ctx.cpp -- libsketch C-ABI (include/sketch.h): the context's
 // lifecycle, options, the sticky error word, streams, host -> device staging,
 // pass timing, the scratch-use ordering and graph capture.  The other
-// subsystems are sketch_api_{bloom,hll,swipes,ingest,cms,hh,tp,tally,seen}.cpp (map: sketch_ctx.h).
+// subsystems are sketch_api_{bloom,hll,swipes,ingest,cms,hh,tp,tally,seen,rows}.cpp (map: sketch_ctx.h).
 #include <stdlib.h>
 #include <string.h>
 
@@ -175,7 +175,7 @@ static int scratch_user_begin(ske_ctx *c, ScratchUse &u, hipStream_t st, unsigne
 
 // the bit of a group in ske_ctx::cap_users / graph_users
 static unsigned scratch_use_bit(const ske_ctx *c, const ScratchUse *u) {
-    return u == &c->sn ? 4u : u == &c->rt ? 2u : 1u;
+    return u == &c->rw ? 8u : u == &c->sn ? 4u : u == &c->rt ? 2u : 1u;
 }
 
 ScratchUser::ScratchUser(ske_ctx *c, ScratchUse &u, hipStream_t st) : c_(c), u_(u), st_(st) {
@@ -311,6 +311,10 @@ const char *ske_strerror(int code) {
     case SKE_ESEENEXISTS: return "ERR seen set already exists";
     case SKE_ESEENCAP: return "ERR seen set capacity out of range";
     case SKE_ESEENCALLS: return "ERR seen set has run out of call numbers";
+    case SKE_EROWSNOLOG: return "ERR row log does not exist";
+    case SKE_EROWSEXISTS: return "ERR row log already exists";
+    case SKE_EROWSCAP: return "ERR row log capacity out of range";
+    case SKE_EROWSSPACE: return "ERR row log selection does not fit the output";
     default: return "ERR unknown";
     }
 }
@@ -374,6 +378,10 @@ int ske_open(int device, ske_ctx **out) {
         const unsigned long long grid = strtoull(v, nullptr, 10);
         c->seen_grid = int(grid < kSeenMaxGrid ? grid : kSeenMaxGrid);
     }
+    if (const char *v = getenv("SKE_ROWS_GRID")) {
+        const unsigned long long grid = strtoull(v, nullptr, 10);
+        c->rows_grid = int(grid < kRowsMaxGrid ? grid : kRowsMaxGrid);
+    }
     if (hipMalloc(&c->zero16, 64) != hipSuccess || hipMemset(c->zero16, 0, 64) != hipSuccess) {
         ske_close(c);
         return SKE_ENOMEM;
@@ -392,6 +400,7 @@ int ske_close(ske_ctx *c) {
     for (auto &P : c->tp) free_tp(P);
     for (auto &Y : c->tally) free_tally(Y);
     for (auto &S : c->seen) free_seen(S);
+    for (auto &R : c->rows) free_rows(R);
     if (c->regs) (void)hipFree(c->regs);
     if (c->tau) (void)hipFree(c->tau);
     if (c->sig) (void)hipFree(c->sig);
@@ -403,6 +412,7 @@ int ske_close(ske_ctx *c) {
     if (c->xr.done) (void)hipEventDestroy(c->xr.done);
     if (c->rt.done) (void)hipEventDestroy(c->rt.done);
     if (c->sn.done) (void)hipEventDestroy(c->sn.done);
+    if (c->rw.done) (void)hipEventDestroy(c->rw.done);
     for (auto &m : c->marks) {
         if (m.own_a) (void)hipEventDestroy(m.a);
         (void)hipEventDestroy(m.b);
@@ -429,7 +439,7 @@ int ske_set_stream(ske_ctx *c, void *stream) {
     hipStream_t next = stream ? (hipStream_t)stream : c->own;
     // leaving the stream of the last scratch use: cover it now, while the
     // stream is known to be alive
-    for (ScratchUse *u : {&c->xr, &c->rt, &c->sn})
+    for (ScratchUse *u : {&c->xr, &c->rt, &c->sn, &c->rw})
         if (next != c->st && u->pending && u->stream == c->st) {
             bool covered = false;
             const int rc = xr_flush(c, *u, &covered);
@@ -609,7 +619,7 @@ int ske_capture_end(ske_ctx *c, void **graph_out) {
 int ske_graph_launch(ske_ctx *c, void *graph) {
     if (!c || !graph) return SKE_EINVAL;
     // a direct scratch use on another stream before the replay
-    for (ScratchUse *u : {&c->xr, &c->rt, &c->sn})
+    for (ScratchUse *u : {&c->xr, &c->rt, &c->sn, &c->rw})
         if (u->done && u->stream && u->stream != c->st && u->cap == 0) {
             bool covered = false;
             const int rc = xr_flush(c, *u, &covered);
@@ -620,11 +630,11 @@ int ske_graph_launch(ske_ctx *c, void *graph) {
     // a replay may hold scratch users (the partitioned / XCD-partitioned K1,
     // routing): a later direct launch on another stream waits for it.  Only
     // the users the graph recorded are marked (a graph of unknown origin:
-    // both).  Two replays of graphs holding scratch users on different
+    // all).  Two replays of graphs holding scratch users on different
     // streams are not ordered by this; replay such graphs on one stream.
     const auto gu = c->graph_users.find(graph);
-    const unsigned users = gu == c->graph_users.end() ? 7u : gu->second;
-    for (ScratchUse *u : {&c->xr, &c->rt, &c->sn})
+    const unsigned users = gu == c->graph_users.end() ? 15u : gu->second;
+    for (ScratchUse *u : {&c->xr, &c->rt, &c->sn, &c->rw})
         if (u->done && (users & scratch_use_bit(c, u))) {
             HIPCHK(c, hipEventRecord(u->done, c->st));
             u->stream = c->st;

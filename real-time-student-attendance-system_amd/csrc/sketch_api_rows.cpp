@@ -1,0 +1,414 @@
+// sketch_api_rows.cpp -- libsketch C-ABI (include/sketch.h): row logs, the
+// attendance table's rows in arrival order (init, reset, info, the three
+// appends, select, read), kernels in sketch_rows.hip.  A log is one device
+// allocation owned by the context and addressed by rid.
+#include <string.h>
+
+#include "sketch_ctx.h"
+
+using namespace ske;
+
+static_assert(kRowsBlock == SKE_ROWS_BLOCK, "sketch.h states the append's tile");
+static_assert(SKE_MAX_ROWS == 8 && SKE_ROWS_MIN_LOG2 >= SKE_SEEN_MIN_LOG2 && SKE_ROWS_MAX_LOG2 <= 28,
+              "the limits sketch.h states; a position fits a u32");
+static_assert(sizeof(ske_rows_info_t) == 48, "six u64 words");
+static_assert(SKE_EROWSNOLOG == -42 && SKE_EROWSEXISTS == -43 && SKE_EROWSCAP == -44 && SKE_EROWSSPACE == -45,
+              "the row-log error codes");
+static_assert(SKE_ROWS_ROW_BYTES == 25, "three words and a byte");
+
+namespace {
+
+constexpr size_t kRowsHeadBytes = 64;
+static_assert(sizeof(RowsHead) <= kRowsHeadBytes, "the head fits its 64 bytes");
+
+}  // namespace
+
+namespace ske {
+
+void free_rows(Rows &R) {
+    if (R.base) (void)hipFree(R.base);
+    R = Rows{};
+}
+
+}  // namespace ske
+
+static Rows *get_rows(ske_ctx *c, uint32_t rid) {
+    return rid < c->rows.size() && c->rows[rid].base ? &c->rows[rid] : nullptr;
+}
+
+// the log of a rid in use for a call that waits for the stream (so it cannot
+// be recorded); rc: why not
+static Rows *rows_for_sync_call(ske_ctx *c, uint32_t rid, const char *what, int *rc) {
+    if (rid >= SKE_MAX_ROWS) return *rc = SKE_EINVAL, nullptr;
+    Rows *R = get_rows(c, rid);
+    if (!R) return *rc = SKE_EROWSNOLOG, nullptr;
+    if (c->capturing) {
+        c->last_hip = std::string(what) + " waits for the stream and cannot be recorded";
+        return *rc = SKE_EBUSY, nullptr;
+    }
+    return R;
+}
+
+static RowsLog log_of(const Rows &R) {
+    const uint64_t cap = uint64_t(1) << R.log2;
+    RowsLog L{};
+    L.head = reinterpret_cast<RowsHead *>(R.base);
+    uint8_t *p = R.base + kRowsHeadBytes;
+    L.lec = reinterpret_cast<unsigned long long *>(p);
+    L.epoch = reinterpret_cast<long long *>(p + cap * 8);
+    L.id = reinterpret_cast<long long *>(p + cap * 16);
+    L.valid = p + cap * 24;
+    L.capacity = cap;
+    return L;
+}
+
+static int rows_head(ske_ctx *c, const Rows &R, RowsHead *h) {
+    HIPCHK(c, hipMemcpyAsync(h, R.base, sizeof(RowsHead), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SKE_OK;
+}
+
+// the four kernels on the context stream; the per-item state is context
+// scratch, ordered behind the previous append's on another stream
+static int rows_enqueue(ske_ctx *c, const Rows &R, RowsItems I) {
+    ScratchUser use(c, c->rw, c->st);
+    if (use.rc) return use.rc;
+    hipError_t e = hipSuccess;
+    RowsWork W{};
+    W.flag = (uint8_t *)scratch_get(c->scratch, kScrRowsFlag, I.n, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    W.idv = (long long *)scratch_get(c->scratch, kScrRowsIdv, uint64_t(I.n) * 8, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    W.cnt = (uint32_t *)scratch_get(c->scratch, kScrRowsCnt, rows_cnt_bytes(I.n), &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    HIPCHK(c, launch_rows_append(log_of(R), I, W, unsigned(c->rows_grid), c->cus, c->st));
+    return SKE_OK;
+}
+
+static int append_args(ske_ctx *c, uint32_t rid, uint64_t n, const int64_t *epoch, Rows **R) {
+    if (!c || rid >= SKE_MAX_ROWS) return SKE_EINVAL;
+    *R = get_rows(c, rid);
+    if (!*R) return SKE_EROWSNOLOG;
+    if (n >= 0xffffffffull) return SKE_EINVAL;
+    if (n && (!epoch || (reinterpret_cast<uintptr_t>(epoch) & 7))) return SKE_EINVAL;
+    return SKE_OK;
+}
+
+extern "C" {
+
+int ske_rows_init(ske_ctx *c, uint32_t rid, uint32_t capacity_log2) {
+    if (!c || rid >= SKE_MAX_ROWS) return SKE_EINVAL;
+    if (capacity_log2 < SKE_ROWS_MIN_LOG2 || capacity_log2 > SKE_ROWS_MAX_LOG2) return SKE_EROWSCAP;
+    if (get_rows(c, rid)) return SKE_EROWSEXISTS;
+    if (c->rows.size() <= rid) c->rows.resize(SKE_MAX_ROWS);
+    Rows R;
+    R.log2 = capacity_log2;
+    R.bytes = kRowsHeadBytes + (size_t(1) << capacity_log2) * SKE_ROWS_ROW_BYTES;
+    hipError_t e = hipMalloc(&R.base, R.bytes);
+    if (e != hipSuccess) {
+        c->last_hip = std::string("hipMalloc(rows): ") + hipGetErrorString(e);
+        return SKE_ENOMEM;
+    }
+    // an empty log: the head zero (the columns are read below `used` only)
+    e = hipMemsetAsync(R.base, 0, kRowsHeadBytes, c->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
+    if (e != hipSuccess) {
+        free_rows(R);
+        c->last_hip = std::string("hipMemset(rows): ") + hipGetErrorString(e);
+        return SKE_EHIP;
+    }
+    c->rows[rid] = R;
+    return SKE_OK;
+}
+
+int ske_rows_free(ske_ctx *c, uint32_t rid) {
+    if (!c || rid >= SKE_MAX_ROWS) return SKE_EINVAL;
+    Rows *R = get_rows(c, rid);
+    if (!R) return SKE_EROWSNOLOG;
+    if (c->live_graphs > 0 || c->capturing) {
+        c->last_hip = "a row log cannot be freed while a recorded graph may point to it";
+        return SKE_EBUSY;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    free_rows(*R);
+    return SKE_OK;
+}
+
+int ske_rows_reset(ske_ctx *c, uint32_t rid) {
+    if (!c) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Rows *R = rows_for_sync_call(c, rid, "ske_rows_reset", &rc);
+    if (!R) return rc;
+    HIPCHK(c, hipMemsetAsync(R->base, 0, kRowsHeadBytes, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SKE_OK;
+}
+
+int ske_rows_info(ske_ctx *c, uint32_t rid, ske_rows_info_t *out) {
+    if (!c || !out) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Rows *R = rows_for_sync_call(c, rid, "ske_rows_info", &rc);
+    if (!R) return rc;
+    RowsHead h{};
+    rc = rows_head(c, *R, &h);
+    if (rc) return rc;
+    out->capacity = uint64_t(1) << R->log2;
+    out->used = h.used;
+    out->taken = h.taken;
+    out->refused_ids = h.refused_ids;
+    out->dropped = h.dropped;
+    out->overflow = h.overflow;
+    return SKE_OK;
+}
+
+int ske_rows_append_packed_async(ske_ctx *c, uint32_t rid, const uint8_t *lec_bytes, const uint32_t *lec_offs,
+                                 const uint8_t *id_bytes, const uint32_t *id_offs, const int64_t *epoch,
+                                 const uint8_t *valid, const uint8_t *mask, uint64_t n) {
+    Rows *R = nullptr;
+    const int rc = append_args(c, rid, n, epoch, &R);
+    if (rc || n == 0) return rc;
+    if (!lec_bytes || !lec_offs || !id_bytes || !id_offs) return SKE_EINVAL;
+    RowsItems I{};
+    I.kind = 0;
+    I.lec_bytes = lec_bytes;
+    I.lec_offs = lec_offs;
+    I.id_bytes = id_bytes;
+    I.id_offs = id_offs;
+    I.epoch = epoch;
+    I.valid = valid;
+    I.mask = mask;
+    I.n = uint32_t(n);
+    return rows_enqueue(c, *R, I);
+}
+
+int ske_rows_append_spans_async(ske_ctx *c, uint32_t rid, const uint8_t *bytes, const uint32_t *lec_start,
+                                const uint32_t *lec_len, const uint32_t *id_start, const uint32_t *id_len,
+                                const uint8_t *status, const int64_t *epoch, const uint8_t *valid,
+                                const uint8_t *mask, uint64_t n) {
+    Rows *R = nullptr;
+    const int rc = append_args(c, rid, n, epoch, &R);
+    if (rc || n == 0) return rc;
+    if (!bytes || !lec_start || !lec_len || !id_start || !id_len) return SKE_EINVAL;
+    RowsItems I{};
+    I.kind = 2;
+    I.lec_bytes = bytes;
+    I.lec_offs = lec_start;
+    I.lec_len = lec_len;
+    I.id_bytes = bytes;
+    I.id_offs = id_start;
+    I.id_len = id_len;
+    I.status = status;
+    I.epoch = epoch;
+    I.valid = valid;
+    I.mask = mask;
+    I.n = uint32_t(n);
+    return rows_enqueue(c, *R, I);
+}
+
+int ske_rows_append_fixed_async(ske_ctx *c, uint32_t rid, const uint8_t *lec_bytes, const uint32_t *lec_offs,
+                                const uint8_t *ids, uint32_t width, const int64_t *epoch, const uint8_t *valid,
+                                const uint8_t *mask, uint64_t n) {
+    Rows *R = nullptr;
+    const int rc = append_args(c, rid, n, epoch, &R);
+    if (rc) return rc;
+    if (width != 4 && width != 8) return SKE_EINVAL;
+    if (n == 0) return SKE_OK;
+    if (!lec_bytes || !lec_offs || !ids) return SKE_EINVAL;
+    RowsItems I{};
+    I.kind = 1;
+    I.lec_bytes = lec_bytes;
+    I.lec_offs = lec_offs;
+    I.id_bytes = ids;
+    I.id_width = width;
+    I.epoch = epoch;
+    I.valid = valid;
+    I.mask = mask;
+    I.n = uint32_t(n);
+    return rows_enqueue(c, *R, I);
+}
+
+// a packed host column on the device: the byte range [offs[0], offs[n]) and the
+// offsets, the bytes pointer rebased so that offs[] index it unchanged
+static int rows_stage_col(ske_ctx *c, const uint8_t *bytes, const uint32_t *offs, uint64_t n, StageSlot sb,
+                          StageSlot so, const uint8_t **d_bytes, const uint32_t **d_offs) {
+    if (!offs) return SKE_EINVAL;
+    for (uint64_t i = 0; i < n; i++)
+        if (offs[i + 1] < offs[i]) return SKE_EINVAL;
+    const uint64_t b0 = offs[0], total = uint64_t(offs[n]) - b0;
+    if (total && !bytes) return SKE_EINVAL;
+    int rc = SKE_OK;
+    uint8_t *db = (uint8_t *)stage_buf(c, sb, total + 16, &rc);
+    if (rc) return rc;
+    uint32_t *dof = (uint32_t *)stage_buf(c, so, (n + 1) * 4, &rc);
+    if (rc) return rc;
+    if (total) HIPCHK(c, hipMemcpyAsync(db, bytes + b0, total, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(dof, offs, (n + 1) * 4, hipMemcpyHostToDevice, c->st));
+    *d_bytes = db - b0;
+    *d_offs = dof;
+    return SKE_OK;
+}
+
+int ske_rows_append(ske_ctx *c, uint32_t rid, const uint8_t *lec_bytes, const uint32_t *lec_offs,
+                    const uint8_t *id_bytes, const uint32_t *id_offs, const int64_t *epoch, const uint8_t *valid,
+                    const uint8_t *mask, uint64_t n, int mem) {
+    if (!c) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Rows *R = rows_for_sync_call(c, rid, "ske_rows_append", &rc);
+    if (!R) return rc;
+    if (n >= 0xffffffffull) return SKE_EINVAL;
+    if (n == 0) return SKE_OK;
+    if (!lec_offs || !id_offs || !epoch) return SKE_EINVAL;
+    RowsItems I{};
+    I.kind = 0;
+    I.n = uint32_t(n);
+    if (mem == SKE_MEM_DEVICE) {
+        if (!lec_bytes || !id_bytes || (reinterpret_cast<uintptr_t>(epoch) & 7)) return SKE_EINVAL;
+        I.lec_bytes = lec_bytes;
+        I.lec_offs = lec_offs;
+        I.id_bytes = id_bytes;
+        I.id_offs = id_offs;
+        I.epoch = epoch;
+        I.valid = valid;
+        I.mask = mask;
+    } else {
+        rc = rows_stage_col(c, lec_bytes, lec_offs, n, kStgRowsLec, kStgRowsLecOffs, &I.lec_bytes, &I.lec_offs);
+        if (rc) return rc;
+        rc = rows_stage_col(c, id_bytes, id_offs, n, kStgRowsId, kStgRowsIdOffs, &I.id_bytes, &I.id_offs);
+        if (rc) return rc;
+        int64_t *de = (int64_t *)stage_buf(c, kStgRowsEpoch, n * 8, &rc);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(de, epoch, n * 8, hipMemcpyHostToDevice, c->st));
+        I.epoch = de;
+        // the valid and mask bytes share one buffer: valid at 0, mask behind it
+        if (valid || mask) {
+            const size_t half = (n + 15) & ~size_t(15);
+            uint8_t *dv = (uint8_t *)stage_buf(c, kStgRowsValid, 2 * half, &rc);
+            if (rc) return rc;
+            if (valid) {
+                HIPCHK(c, hipMemcpyAsync(dv, valid, n, hipMemcpyHostToDevice, c->st));
+                I.valid = dv;
+            }
+            if (mask) {
+                HIPCHK(c, hipMemcpyAsync(dv + half, mask, n, hipMemcpyHostToDevice, c->st));
+                I.mask = dv + half;
+            }
+        }
+    }
+    rc = rows_enqueue(c, *R, I);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SKE_OK;
+}
+
+int ske_rows_read(ske_ctx *c, uint32_t rid, uint64_t first, uint64_t n, uint64_t *out_lec, int64_t *out_epoch,
+                  int64_t *out_id, uint8_t *out_valid) {
+    if (!c) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Rows *R = rows_for_sync_call(c, rid, "ske_rows_read", &rc);
+    if (!R) return rc;
+    RowsHead h{};
+    rc = rows_head(c, *R, &h);
+    if (rc) return rc;
+    if (first > h.used || n > h.used - first) return SKE_EINVAL;
+    if (n == 0) return SKE_OK;
+    if (!out_lec || !out_epoch || !out_id || !out_valid) return SKE_EINVAL;
+    const RowsLog L = log_of(*R);
+    HIPCHK(c, hipMemcpyAsync(out_lec, L.lec + first, n * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(out_epoch, L.epoch + first, n * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(out_id, L.id + first, n * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(out_valid, L.valid + first, n, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SKE_OK;
+}
+
+int ske_rows_select(ske_ctx *c, uint32_t rid, const uint8_t *lec_bytes, uint32_t lec_len, int64_t since,
+                    int64_t until, uint64_t *out_lec, int64_t *out_epoch, int64_t *out_id, uint8_t *out_valid,
+                    uint64_t cap, uint64_t *n_out, int *complete, int mem) {
+    if (!c || !n_out || !complete) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Rows *R = rows_for_sync_call(c, rid, "ske_rows_select", &rc);
+    if (!R) return rc;
+    if (cap && (!out_lec || !out_epoch || !out_id || !out_valid)) return SKE_EINVAL;
+    RowsHead h{};
+    rc = rows_head(c, *R, &h);
+    if (rc) return rc;
+    *n_out = 0;
+    *complete = h.overflow ? 0 : 1;
+    const uint32_t used = uint32_t(h.used);  // <= 2^28
+    if (used == 0) return SKE_OK;
+    const RowsLog L = log_of(*R);
+    const bool by_lec = lec_bytes != nullptr || lec_len != 0;
+    if (lec_len && !lec_bytes) return SKE_EINVAL;
+    const unsigned long long digest = by_lec ? rows_lecture_digest(lec_bytes, lec_len) : 0;
+
+    hipError_t e = hipSuccess;
+    RowsWork W{};
+    W.flag = (uint8_t *)scratch_get(c->scratch, kScrRowsSelFlag, used, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    W.cnt = (uint32_t *)scratch_get(c->scratch, kScrRowsSelCnt, rows_cnt_bytes(used), &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    uint32_t *pos = (uint32_t *)scratch_get(c->scratch, kScrVals, uint64_t(used) * 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    const unsigned grid = unsigned(c->rows_grid);
+
+    // 1, 2: the matching positions, ascending
+    HIPCHK(c, launch_rows_match(L, used, by_lec, digest, since, until, W, pos, grid, c->cus, c->st));
+    uint32_t m = 0;
+    HIPCHK(c, hipMemcpyAsync(&m, W.cnt, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (m == 0) return SKE_OK;
+
+    // 3: one stable pass per column, the least significant first
+    unsigned long long *keys = (unsigned long long *)scratch_get(c->scratch, kScrKeysOrFirst, uint64_t(m) * 8, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    unsigned long long *keys_s = (unsigned long long *)scratch_get(c->scratch, kScrKeysSorted, uint64_t(m) * 8, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    uint32_t *pos_s = (uint32_t *)scratch_get(c->scratch, kScrValsSorted, uint64_t(m) * 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    uint32_t *cur = pos, *nxt = pos_s;
+    const int passes = by_lec ? 2 : 3;
+    for (int col = 0; col < passes; col++) {
+        HIPCHK(c, launch_rows_keys(L, cur, m, col, keys, grid, c->cus, c->st));
+        e = rows_sort_pairs(c->scratch, col < 2, keys, keys_s, cur, nxt, m, c->st);
+        if (e == hipErrorStreamCaptureUnsupported) return scratch_error(c, e);
+        HIPCHK(c, e);
+        uint32_t *t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+
+    // 4: the last-appended row of each run of equal keys
+    HIPCHK(c, launch_rows_last(L, cur, m, W, grid, c->cus, c->st));
+    uint32_t runs = 0;
+    HIPCHK(c, hipMemcpyAsync(&runs, W.cnt, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    *n_out = runs;
+    if (runs > cap) return SKE_EROWSSPACE;
+
+    // 5: the columns
+    uint64_t *d_lec = out_lec;
+    int64_t *d_epoch = out_epoch, *d_id = out_id;
+    uint8_t *d_valid = out_valid;
+    if (mem != SKE_MEM_DEVICE) {
+        d_lec = (uint64_t *)stage_buf(c, kStgRowsLec, uint64_t(runs) * 8, &rc);
+        if (rc) return rc;
+        d_epoch = (int64_t *)stage_buf(c, kStgRowsEpoch, uint64_t(runs) * 8, &rc);
+        if (rc) return rc;
+        d_id = (int64_t *)stage_buf(c, kStgRowsId, uint64_t(runs) * 8, &rc);
+        if (rc) return rc;
+        d_valid = (uint8_t *)stage_buf(c, kStgRowsValid, runs, &rc);
+        if (rc) return rc;
+    }
+    HIPCHK(c, launch_rows_gather(L, cur, m, W, (unsigned long long *)d_lec, (long long *)d_epoch, (long long *)d_id,
+                                 d_valid, grid, c->cus, c->st));
+    if (mem != SKE_MEM_DEVICE) {
+        HIPCHK(c, hipMemcpyAsync(out_lec, d_lec, uint64_t(runs) * 8, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipMemcpyAsync(out_epoch, d_epoch, uint64_t(runs) * 8, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipMemcpyAsync(out_id, d_id, uint64_t(runs) * 8, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipMemcpyAsync(out_valid, d_valid, runs, hipMemcpyDeviceToHost, c->st));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SKE_OK;
+}
+
+}  // extern "C"

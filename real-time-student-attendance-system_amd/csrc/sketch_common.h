@@ -193,6 +193,64 @@ SKE_HD uint32_t seen_start(uint64_t k0, uint32_t capacity_log2) {
 }
 SKE_HD uint64_t seen_limit(uint32_t capacity_log2) { return (uint64_t(1) << capacity_log2) / kSeenLoadDen; }
 
+// Row logs (sketch_rows.hip): the attendance table's rows, appended in arrival
+// order.  A row's partition is its lecture's digest -- the tally's identity rule
+// (tally_digest above) over a lecture of any length: MurmurHash64A of the
+// lecture bytes, the Bloom seed, 0 mapped to 1 -- so a tally listing names the
+// log's partitions.  Two lectures with equal digests are one partition.
+constexpr int kRowsBlock = 256;         // items per workgroup and tile of an append (SKE_ROWS_BLOCK)
+constexpr uint32_t kRowsIdMaxLen = 20;  // "-9223372036854775808"
+SKE_HD uint64_t rows_lecture_word(uint64_t murmur) { return murmur ? murmur : 1; }
+// the digest from byte loads alone (host restatement of murmur_item's arithmetic)
+SKE_HD uint64_t rows_lecture_digest(const uint8_t *p, uint32_t len) {
+    uint64_t h = kBloomSeed ^ (uint64_t(len) * kMurmurM);
+    const uint32_t nblk = len >> 3, rem = len & 7;
+    for (uint32_t j = 0; j < nblk; j++, p += 8) {
+        uint64_t k = 0;
+        for (uint32_t b = 0; b < 8; b++) k |= uint64_t(p[b]) << (8 * b);
+        h = mm_block(h, k);
+    }
+    if (rem) {
+        uint64_t t = 0;
+        for (uint32_t b = 0; b < rem; b++) t |= uint64_t(p[b]) << (8 * b);
+        h ^= t;
+        h *= kMurmurM;
+    }
+    return rows_lecture_word(mm_final(h));
+}
+// The id column is Cassandra's `student_id int`: the id's text must be canonical
+// decimal -- "-"? then digits, no leading zero except "0" itself, no "-0", no
+// "+", no blanks -- and fit int64.  The text is its first 24 bytes as three
+// little-endian words, zero padded (len <= kRowsIdMaxLen matters, longer is
+// refused unread).  false: not an integer, the row is refused.
+SKE_HD bool rows_parse_id(uint64_t w0, uint64_t w1, uint64_t w2, uint32_t len, int64_t *out) {
+    if (len == 0 || len > kRowsIdMaxLen) return false;
+    const uint32_t neg = (w0 & 0xff) == '-' ? 1u : 0u;
+    const uint32_t ndig = len - neg;
+    if (ndig == 0 || ndig > 19) return false;
+    uint64_t v = 0;
+    bool ok = true;
+    uint32_t first = 0;
+    for (uint32_t j = neg; j < len; j++) {
+        const uint64_t w = j < 8 ? w0 : (j < 16 ? w1 : w2);
+        const uint32_t ch = uint32_t(w >> (8 * (j & 7))) & 0xff;
+        const uint32_t d = ch - '0';
+        ok = ok && d <= 9;
+        if (j == neg) first = d;
+        v = v * 10 + d;  // 19 digits stay below 2^64
+    }
+    if (!ok) return false;
+    if (first == 0 && (ndig > 1 || neg)) return false;
+    if (neg) {
+        if (v > (uint64_t(1) << 63)) return false;
+        *out = int64_t(~v + 1);
+    } else {
+        if (v > (uint64_t(1) << 63) - 1) return false;
+        *out = int64_t(v);
+    }
+    return true;
+}
+
 // ---------------------------------------------------------------------------
 // MurmurHash2, the 32-bit form (RedisBloom deps/murmur2/MurmurHash2.c
 // MurmurHash2): the Count-Min Sketch's row hash, cell of row i =

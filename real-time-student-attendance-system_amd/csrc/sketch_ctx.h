@@ -13,6 +13,7 @@
 //   sketch_api_tp.cpp      time profiles (weekday x hour counters): init, add, read / import
 //   sketch_api_tally.cpp   tallies (exact event counts per key): init, add, query, list, top, import
 //   sketch_api_seen.cpp    seen-row sets (exact sets of 128-bit row keys): init, the folds, add, test
+//   sketch_api_rows.cpp    row logs (the attendance rows in arrival order): init, append, select, read
 // A helper used by one unit is static there; what crosses units is declared here.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -91,6 +92,14 @@ struct Seen {
     uint64_t calls_host = 0;
 };
 
+// one row log (base == nullptr: the rid is free); one allocation: a 64-byte
+// head (RowsHead), then the lec, epoch and id words and the valid bytes
+struct Rows {
+    uint8_t *base = nullptr;
+    size_t bytes = 0;
+    uint32_t log2 = 0;
+};
+
 struct Staged {
     const uint8_t *bytes = nullptr;
     const uint32_t *offs = nullptr;
@@ -142,6 +151,10 @@ struct ske_ctx {
     // workgroups of the seen sets' kernels (SKE_SEEN_GRID, read by ske_open; 0:
     // eight per CU); for small-shape tests, changes no result
     int seen_grid = 0;
+    std::vector<ske::Rows> rows;  // by rid (sized on first use)
+    // workgroups of the row logs' kernels (SKE_ROWS_GRID, read by ske_open; 0:
+    // eight per CU); for small-shape tests, changes no result
+    int rows_grid = 0;
     // workgroups of ske_ingest_times / ske_ingest_dense (SKE_INGEST_GRID, read by
     // ske_open; 0: the ingest kernels' launch shape); for small-shape tests, changes no result
     int ingest_grid = 0;
@@ -171,12 +184,13 @@ struct ske_ctx {
     ske::ScratchUse xr;  // K1's slots (kScrXr, kScrPart*, kScrSeg*)
     ske::ScratchUse rt;  // routing's slots (kScrRoute*): ordered among routing calls, not behind K1
     ske::ScratchUse sn;  // the seen sets' slot (kScrSeenSlot): ordered among seen adds alone
+    ske::ScratchUse rw;  // the row logs' slots (kScrRowsFlag, Idv, Cnt): ordered among appends alone
     // executable graphs alive (recorded, not yet freed): they hold pointers to
     // the scratch and the register slab, so neither may be reallocated
     int live_graphs = 0;
     bool capturing = false;
     // scratch users recorded into the graph being captured (bit 0: xr,
-    // bit 1: rt, bit 2: sn), and per live graph the users its replays hold: a replay
+    // bit 1: rt, bit 2: sn, bit 3: rw), and per live graph the users its replays hold: a replay
     // records only their events, so a graph without routing does not order
     // the next routing call behind itself
     unsigned cap_users = 0;
@@ -255,7 +269,7 @@ private:
     bool open_ = false;  // begun, end event not yet recorded
 };
 
-// One use of an ordering group of the context scratch (c->xr, c->rt or c->sn) by what
+// One use of an ordering group of the context scratch (c->xr, c->rt, c->sn or c->rw) by what
 // is enqueued on `st` while the guard lives: the constructor makes st wait for
 // the group's last use on another stream (rc != 0: it failed, nothing may be
 // launched), the destructor notes this use on every exit after that.
@@ -310,6 +324,9 @@ void free_tally(Tally &Y);
 
 // ---- sketch_api_seen.cpp
 void free_seen(Seen &S);
+
+// ---- sketch_api_rows.cpp
+void free_rows(Rows &R);
 
 // ---- sketch_api_swipes.cpp
 bool use_lds(const ske_ctx *c, const ChainDev &ch);

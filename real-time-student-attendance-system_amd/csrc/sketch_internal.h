@@ -413,6 +413,75 @@ hipError_t launch_seen_add(const SeenTab &T, const uint64_t *keys, uint32_t n, c
 hipError_t launch_seen_test(const SeenTab &T, const uint64_t *keys, uint32_t n, uint8_t *present, unsigned grid,
                             int cus, hipStream_t st);
 
+// sketch_rows.hip -- row logs: the attendance table's rows in arrival order, an
+// append-only columnar log read back per lecture (DESIGN.md "Row log")
+constexpr unsigned kRowsMaxGrid = 4096;
+constexpr unsigned kRowsScanBlock = 1024;  // threads of the one workgroup that scans the tile counts
+struct RowsHead {  // the first bytes of a log's allocation
+    unsigned long long used;         // rows held: the next row's position
+    unsigned long long taken;        // rows the statuses and masks let through
+    unsigned long long refused_ids;  // of those, the ones whose id is not an integer
+    unsigned long long dropped;      // of those, the ones that found the log full
+    unsigned int overflow;           // sticky: a row was dropped
+};
+struct RowsLog {
+    RowsHead *head;
+    unsigned long long *lec;  // per row: the lecture's digest
+    long long *epoch;         //   seconds
+    long long *id;            //   the student id
+    uint8_t *valid;           //   is_valid
+    uint64_t capacity;
+};
+// where a batch's lecture and id columns are: kind 0 both packed, 1 lectures
+// packed and ids fixed width (4 or 8 little-endian bytes), 2 both spans of bytes
+struct RowsItems {
+    int kind;
+    const uint8_t *lec_bytes;
+    const uint32_t *lec_offs;  // kind 0, 1: offsets; kind 2: starts
+    const uint32_t *lec_len;   // kind 2
+    const uint8_t *id_bytes;
+    const uint32_t *id_offs;   // kind 0: offsets; kind 2: starts
+    const uint32_t *id_len;    // kind 2
+    uint32_t id_width;         // kind 1
+    const int64_t *epoch;
+    const uint8_t *valid;      // may be null: every row's is_valid is 0
+    const uint8_t *status;     // may be null; else rows with status[i] == 0
+    const uint8_t *mask;       // may be null; else rows with mask[i] == 1
+    uint32_t n;
+};
+// per-call state of an append or a select: a flag byte and a parsed id per
+// item, and per tile of kRowsBlock items two counts behind a 4-word total
+struct RowsWork {
+    uint8_t *flag;   // n bytes: 0 not taken, 1 placed, 2 refused
+    long long *idv;  // n parsed ids (append)
+    uint32_t *cnt;   // [0..3] totals, then tiles placed-counts, then tiles refused-counts
+};
+SKE_HD uint64_t rows_tiles(uint64_t n) { return (n + kRowsBlock - 1) / kRowsBlock; }
+inline size_t rows_cnt_bytes(uint64_t n) { return (4 + 2 * rows_tiles(n)) * 4; }
+// flag and count, scan, place, then the head's advance; grid: workgroups (0: eight per CU)
+hipError_t launch_rows_append(const RowsLog &L, const RowsItems &I, const RowsWork &W, unsigned grid, int cus,
+                              hipStream_t st);
+// flag[i] = row i < m is of the lecture (any when !by_lec) and since <= epoch < until; then the scan:
+// W.cnt[0] = matches, pos_out (positions ascending) filled
+hipError_t launch_rows_match(const RowsLog &L, uint32_t m, bool by_lec, unsigned long long digest, long long since,
+                             long long until, const RowsWork &W, uint32_t *pos_out, unsigned grid, int cus,
+                             hipStream_t st);
+// key_out[j] = column col (0 id, 1 epoch, 2 lec) of row pos[j]
+hipError_t launch_rows_keys(const RowsLog &L, const uint32_t *pos, uint32_t m, int col, unsigned long long *key_out,
+                            unsigned grid, int cus, hipStream_t st);
+// over pos in sorted order: flag[j] = row pos[j] is the last of its run of equal (lec, epoch, id); the
+// scan: W.cnt[0] = runs
+hipError_t launch_rows_last(const RowsLog &L, const uint32_t *pos, uint32_t m, const RowsWork &W, unsigned grid,
+                            int cus, hipStream_t st);
+// the flagged rows' columns, in order, to the outputs (after launch_rows_last)
+hipError_t launch_rows_gather(const RowsLog &L, const uint32_t *pos, uint32_t m, const RowsWork &W,
+                              unsigned long long *out_lec, long long *out_epoch, long long *out_id,
+                              uint8_t *out_valid, unsigned grid, int cus, hipStream_t st);
+// stable radix sort of (key, pos) pairs by key, signed or unsigned 64 bits (sketch_order.hip; the
+// temporary is kScrSortTmp)
+hipError_t rows_sort_pairs(Scratch *s, bool is_signed, const unsigned long long *keys, unsigned long long *keys_s,
+                           const uint32_t *pos, uint32_t *pos_s, uint32_t m, hipStream_t st);
+
 // sketch_hll_fmt.hip -- HLL keys as Redis "HYLL" strings, one key per workgroup
 // (DESIGN.md section 14); the opcode rules are sketch_hll_fmt.h's
 // sizes[i] = length of key i's string (slots == nullptr: keys 0 .. nkeys - 1);
@@ -435,16 +504,17 @@ hipError_t launch_hll_fmt_offs_check(const uint32_t *offs, uint32_t n, unsigned 
 
 // sketch_order.hip -- order-exact paths (replies that depend on item order)
 struct Scratch;  // growable device scratch, owned by the context
-constexpr int kScratchSlots = 56;
+constexpr int kScratchSlots = 64;
 
 // Every slot of the context scratch, by owner (who sizes it) and user.  The
 // numbers carry no meaning beyond identity; a slot belongs to exactly one of
-// three ordering groups:
+// these ordering groups:
 //   sync  used only inside synchronous calls, which run on the context stream
 //         and end with a stream synchronise, so two such calls never overlap;
 //   xr    K1's per-launch state, ordered through ske_ctx::xr (ScratchUser);
 //   rt    routing's, ordered through ske_ctx::rt;
-//   sn    the seen sets' per-item slots, ordered through ske_ctx::sn.
+//   sn    the seen sets' per-item slots, ordered through ske_ctx::sn;
+//   rw    the row logs' per-append state, ordered through ske_ctx::rw.
 // The rule: a slot reachable from an rt-ordered call may have no user ordered
 // through xr, and the other way round -- routing runs beside K1 on another
 // stream (distributed.SwipeExchange's pipelined form), and neither waits for
@@ -452,14 +522,15 @@ constexpr int kScratchSlots = 56;
 enum ScratchSlot : int {
     // -- sync
     kScrKeysOrFirst,   // pfadd_exact: sort keys | ske_bf_madd: a link's first-setter table
-                       // (up to 4 x bits bytes); both synchronous calls, never at once
-    kScrKeysSorted,    // pfadd_exact (sketch_order.hip): sorted keys,
-    kScrVals,          //   element indices,
+                       // (up to 4 x bits bytes) | ske_rows_select: a pass's sort keys; synchronous
+                       // calls all, never at once
+    kScrKeysSorted,    // pfadd_exact (sketch_order.hip), ske_rows_select: sorted keys,
+    kScrVals,          //   element indices (ske_rows_select: row positions),
     kScrValsSorted,    //   sorted indices,
     kScrRank,          //   ranks,
     kScrRankSorted,    //   ranks in sorted order,
     kScrPrefMax,       //   running maximum per register,
-    kScrSortTmp,       //   rocprim radix sort temporary,
+    kScrSortTmp,       //   rocprim radix sort temporary (also ske_rows_select's),
     kScrScanKeyTmp,    //   rocprim scan-by-key temporary
     kScrScanTmp,       // scan_inclusive_u32's rocprim temporary: ske_bf_madd, ske_keytab_lookup,
                        // ske_ingest_swipes, ske_ingest_dense, ske_hll_dump_sizes, ske_hll_dump
@@ -484,6 +555,8 @@ enum ScratchSlot : int {
     kScrHllFmtSize,    // ske_hll_dump_sizes, ske_hll_dump (sketch_api_hll.cpp): a string length per key,
     kScrHllFmtOffs,    //   their exclusive scan (nkeys + 1 offsets),
     kScrHllFmtCard,    //   ske_hll_dump with SKE_HLL_DUMP_CARD: a PFCOUNT per key
+    kScrRowsSelFlag,   // ske_rows_select: a flag byte per row (match, then last of its run),
+    kScrRowsSelCnt,    //   the totals and the per-tile counts of the flags
     // -- xr
     kScrXr,            // launch_k1: the XCD-partitioned K1's state (sketch_xr.hip)
     kScrPartRec,       // part_scratch (sketch_part.hip): probe records,
@@ -509,6 +582,10 @@ enum ScratchSlot : int {
     kScrRouteTot,      // ske_route_swipes: the owners' totals
     // -- sn
     kScrSeenSlot,      // ske_seen_add_async: the slot each item's walk ended at, from the walk to the answers
+    // -- rw
+    kScrRowsFlag,      // ske_rows_append_*_async: a flag byte per item (taken, refused), from the flags to the place,
+    kScrRowsIdv,       //   the parsed id per item,
+    kScrRowsCnt,       //   the totals and the per-tile counts, scanned in place
     kScratchSlotCount
 };
 static_assert(kScratchSlotCount <= kScratchSlots, "Scratch holds kScratchSlots slots");
@@ -546,6 +623,12 @@ enum StageSlot : int {
     kStgSeenKeys,      // ske_seen_add / ske_seen_test: the keys,
     kStgSeenMask,      //   ske_seen_add: a mask byte per item,
     kStgSeenOut,       //   the answers on their way to the host
+    kStgRowsLec,       // ske_rows_append: the lecture bytes | ske_rows_select / ske_rows_read: the digests on their way out,
+    kStgRowsLecOffs,   //   ske_rows_append: the lecture offsets,
+    kStgRowsId,        //   the id bytes | ske_rows_select: the ids on their way to the host,
+    kStgRowsIdOffs,    //   the id offsets,
+    kStgRowsEpoch,     //   the epochs (both directions),
+    kStgRowsValid,     //   the valid bytes (both directions)
     kStageSlotCount
 };
 

@@ -399,4 +399,26 @@ hipError_t launch_bf_fill_rest(uint64_t n, uint8_t *state, int8_t *res, int8_t c
     return hipGetLastError();
 }
 
+// One pass of ske_rows_select's sort (sketch_rows.hip): the radix sort is
+// stable, so sorting by the least significant column first and carrying the
+// positions as values leaves (lec, epoch, id, position) order.
+template <typename Key>
+static hipError_t rows_sort_typed(Scratch *s, const Key *keys, Key *keys_s, const uint32_t *pos, uint32_t *pos_s,
+                                  uint32_t m, hipStream_t st) {
+    size_t tb = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, tb, keys, keys_s, pos, pos_s, size_t(m), 0u, 64u, st);
+    if (e != hipSuccess) return e;
+    void *tmp = scratch_get(s, kScrSortTmp, tb, &e);
+    if (!tmp) return e;
+    return rocprim::radix_sort_pairs(tmp, tb, keys, keys_s, pos, pos_s, size_t(m), 0u, 64u, st);
+}
+hipError_t rows_sort_pairs(Scratch *s, bool is_signed, const unsigned long long *keys, unsigned long long *keys_s,
+                           const uint32_t *pos, uint32_t *pos_s, uint32_t m, hipStream_t st) {
+    if (m == 0) return hipSuccess;
+    if (is_signed)
+        return rows_sort_typed(s, reinterpret_cast<const long long *>(keys), reinterpret_cast<long long *>(keys_s),
+                               pos, pos_s, m, st);
+    return rows_sort_typed(s, keys, keys_s, pos, pos_s, m, st);
+}
+
 }  // namespace ske

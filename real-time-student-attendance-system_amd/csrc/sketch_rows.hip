@@ -1,0 +1,357 @@
+// sketch_rows.hip -- row logs (DESIGN.md "Row log"): the attendance table's rows
+// (lecture digest, epoch, student id, is_valid) as four device columns, appended
+// in arrival order and read back per lecture in the table's clustering order.
+//
+// An append is four launches on one stream, none of which waits for a block of
+// its own launch (sketch_hh.hip's rule: no thread spins on another's progress):
+//   k_rows_flag   per item: taken (status 0, mask 1)?  its id parsed (canonical
+//                 decimal text, or 4 / 8 little-endian bytes); a flag byte and the
+//                 id to scratch, and per tile of kRowsBlock items the count of
+//                 the rows to place and of the refused ids
+//   k_rows_scan   one workgroup: the tile counts to their exclusive prefix, in
+//                 place, kRowsScanBlock tiles a pass; the two totals
+//   k_rows_place  per tile: a row's rank among the tile's rows (wave64 ballot
+//                 and popcount, the waves' totals through LDS), its position
+//                 used + prefix[tile] + rank; rows inside the capacity get their
+//                 lecture's digest and are written
+//   k_rows_end    one thread: the head's advance
+// Every position is a function of the batch and of `used` alone, so the log's
+// contents and layout are the same from run to run, and position order is
+// arrival order within a call and across calls.  `used` lives in the log and
+// is advanced by k_rows_end, never passed as a launch argument: a recorded
+// append that is replayed appends behind what is there.
+//
+// A select reuses the same flag / count / scan machinery twice: over the log's
+// rows (which match), and over the matching positions in sorted order (which
+// is the last of its run of equal keys).  The sort between the two is
+// rows_sort_pairs (sketch_order.hip), one stable pass per key column.
+#include "sketch_common.h"
+#include "sketch_internal.h"
+
+namespace ske {
+namespace {
+
+constexpr int kRowsWaves = kRowsBlock / 64;
+static_assert(kRowsBlock % 64 == 0 && kRowsScanBlock % 64 == 0, "whole wavefronts");
+
+// the tile's two counts to cnt (every thread of the workgroup calls it)
+__device__ __forceinline__ void rows_tile_count(bool ok, bool ref, uint32_t *cnt, uint64_t tiles, uint64_t t,
+                                                unsigned int *s_ok, unsigned int *s_ref) {
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long b_ok = __ballot(ok), b_ref = __ballot(ref);
+    if (lane == 0) {
+        s_ok[w] = uint32_t(__popcll(b_ok));
+        s_ref[w] = uint32_t(__popcll(b_ref));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t a = 0, r = 0;
+#pragma unroll
+        for (int k = 0; k < kRowsWaves; k++) a += s_ok[k], r += s_ref[k];
+        cnt[4 + t] = a;
+        cnt[4 + tiles + t] = r;
+    }
+    __syncthreads();  // the LDS words are written again in the next turn
+}
+
+// the rank of a flagged item among the tile's flagged items, in item order
+__device__ __forceinline__ uint32_t rows_tile_rank(bool ok, unsigned int *s_ok) {
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(ok);
+    if (lane == 0) s_ok[w] = uint32_t(__popcll(b));
+    __syncthreads();
+    uint32_t before = 0;
+#pragma unroll
+    for (int k = 0; k < kRowsWaves; k++)
+        if (uint32_t(k) < w) before += s_ok[k];
+    const uint32_t r = before + uint32_t(__popcll(b & ((1ull << lane) - 1)));
+    __syncthreads();
+    return r;
+}
+
+// the id text of at most kRowsIdMaxLen bytes as three words (only the aligned
+// words that hold a byte of it are read)
+__device__ __forceinline__ bool rows_id_text(const uint8_t *p, uint32_t len, int64_t *out) {
+    if (len == 0 || len > kRowsIdMaxLen) return false;
+    const uint64_t w0 = load_le(p, len < 8 ? len : 8);
+    const uint64_t w1 = len > 8 ? load_le(p + 8, len < 16 ? len - 8 : 8) : 0;
+    const uint64_t w2 = len > 16 ? load_le(p + 16, len - 16) : 0;
+    return rows_parse_id(w0, w1, w2, len, out);
+}
+
+template <int kKind>
+__global__ void __launch_bounds__(kRowsBlock) k_rows_flag(const RowsItems I, const RowsWork W) {
+    __shared__ unsigned int s_ok[kRowsWaves], s_ref[kRowsWaves];
+    const uint64_t tiles = rows_tiles(I.n);
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t i = t * kRowsBlock + threadIdx.x;
+        const bool in = i < I.n;
+        const bool takes = in && (!I.status || I.status[i] == 0) && (!I.mask || I.mask[i] == 1);
+        int64_t v = 0;
+        bool ok = false;
+        if (takes) {
+            if (kKind == 0) {
+                const uint32_t b = I.id_offs[i], e = I.id_offs[i + 1];
+                ok = rows_id_text(I.id_bytes + b, e - b, &v);
+            } else if (kKind == 1) {
+                const uint8_t *p = I.id_bytes + i * I.id_width;
+                v = I.id_width == 8 ? int64_t(load_le(p, 8)) : int64_t(int32_t(uint32_t(load_le(p, 4))));
+                ok = true;
+            } else {
+                ok = rows_id_text(I.id_bytes + I.id_offs[i], I.id_len[i], &v);
+            }
+        }
+        if (in) {
+            W.flag[i] = takes ? (ok ? 1 : 2) : 0;
+            W.idv[i] = v;
+        }
+        rows_tile_count(ok, takes && !ok, W.cnt, tiles, t, s_ok, s_ref);
+    }
+}
+
+// cnt[4 + t] = the placed-counts of the tiles before t; cnt[0] = their total,
+// cnt[1] = the refused-counts' total.  One workgroup: a pass scans
+// kRowsScanBlock tiles (an inclusive scan per wavefront by shuffles, the
+// wavefronts' totals through LDS) and carries its total into the next.
+__global__ void __launch_bounds__(kRowsScanBlock) k_rows_scan(uint32_t *cnt, uint64_t tiles) {
+    constexpr int kWaves = kRowsScanBlock / 64;
+    __shared__ unsigned int s_w[kWaves];
+    __shared__ unsigned int s_ref;
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (threadIdx.x == 0) s_ref = 0;
+    uint32_t carry = 0, ref = 0;
+    for (uint64_t base = 0; base < tiles; base += kRowsScanBlock) {
+        const uint64_t t = base + threadIdx.x;
+        const uint32_t a = t < tiles ? cnt[4 + t] : 0;
+        if (t < tiles) ref += cnt[4 + tiles + t];
+        uint32_t x = a;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t y = __shfl_up(x, d, 64);
+            if (lane >= uint32_t(d)) x += y;
+        }
+        if (lane == 63) s_w[w] = x;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+#pragma unroll
+        for (int k = 0; k < kWaves; k++) {
+            const uint32_t s = s_w[k];
+            if (uint32_t(k) < w) before += s;
+            all += s;
+        }
+        if (t < tiles) cnt[4 + t] = carry + before + x - a;
+        carry += all;
+        __syncthreads();
+    }
+    if (ref) atomicAdd(&s_ref, ref);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        cnt[0] = carry;
+        cnt[1] = s_ref;
+    }
+}
+
+template <int kKind>
+__global__ void __launch_bounds__(kRowsBlock) k_rows_place(const RowsLog L, const RowsItems I, const RowsWork W) {
+    __shared__ unsigned int s_ok[kRowsWaves];
+    const uint64_t tiles = rows_tiles(I.n);
+    const unsigned long long used = L.head->used;  // k_rows_end advances it behind this launch
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t i = t * kRowsBlock + threadIdx.x;
+        const bool ok = i < I.n && W.flag[i] == 1;
+        const uint32_t rank = rows_tile_rank(ok, s_ok);
+        if (!ok) continue;
+        const unsigned long long pos = used + W.cnt[4 + t] + rank;
+        if (pos >= L.capacity) continue;  // the batch's tail: k_rows_end counts it
+        uint32_t b, e;
+        if (kKind == 2) {
+            b = I.lec_offs[i];
+            e = b + I.lec_len[i];
+        } else {
+            b = I.lec_offs[i];
+            e = I.lec_offs[i + 1];
+        }
+        const Item it = load_item(I.lec_bytes, b, e);
+        L.lec[pos] = rows_lecture_word(murmur_item(it, kBloomSeed));
+        L.epoch[pos] = I.epoch[i];
+        L.id[pos] = W.idv[i];
+        L.valid[pos] = I.valid && I.valid[i] ? 1 : 0;
+    }
+}
+
+__global__ void k_rows_end(const RowsLog L, const uint32_t *cnt) {
+    if (blockIdx.x || threadIdx.x) return;
+    RowsHead *h = L.head;
+    const unsigned long long ok = cnt[0], ref = cnt[1];
+    const unsigned long long room = L.capacity - h->used;
+    const unsigned long long kept = ok < room ? ok : room;
+    h->used += kept;
+    h->taken += ok + ref;
+    h->refused_ids += ref;
+    if (ok > kept) {
+        h->dropped += ok - kept;
+        h->overflow = 1;
+    }
+}
+
+// ---- select
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_match(const RowsLog L, uint32_t m, int by_lec,
+                                                            unsigned long long digest, long long since,
+                                                            long long until, const RowsWork W) {
+    __shared__ unsigned int s_ok[kRowsWaves], s_ref[kRowsWaves];
+    const uint64_t tiles = rows_tiles(m);
+    const bool open_end = until == INT64_MAX;
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t i = t * kRowsBlock + threadIdx.x;
+        bool ok = false;
+        if (i < m) {
+            const long long e = L.epoch[i];
+            ok = (!by_lec || L.lec[i] == digest) && e >= since && (open_end || e < until);
+            W.flag[i] = ok ? 1 : 0;
+        }
+        rows_tile_count(ok, false, W.cnt, tiles, t, s_ok, s_ref);
+    }
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_positions(uint32_t m, const RowsWork W, uint32_t *pos_out) {
+    __shared__ unsigned int s_ok[kRowsWaves];
+    const uint64_t tiles = rows_tiles(m);
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t i = t * kRowsBlock + threadIdx.x;
+        const bool ok = i < m && W.flag[i] == 1;
+        const uint32_t rank = rows_tile_rank(ok, s_ok);
+        if (ok) pos_out[W.cnt[4 + t] + rank] = uint32_t(i);
+    }
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_keys(const RowsLog L, const uint32_t *pos, uint32_t m, int col,
+                                                           unsigned long long *key_out) {
+    const uint64_t stride = uint64_t(gridDim.x) * kRowsBlock;
+    for (uint64_t j = uint64_t(blockIdx.x) * kRowsBlock + threadIdx.x; j < m; j += stride) {
+        const uint32_t p = pos[j];
+        key_out[j] = col == 0 ? (unsigned long long)L.id[p] : col == 1 ? (unsigned long long)L.epoch[p] : L.lec[p];
+    }
+}
+
+// pos is sorted by (lec, epoch, id, position): the last row of a run of equal
+// (lec, epoch, id) is the one appended last -- the upsert's survivor
+__global__ void __launch_bounds__(kRowsBlock) k_rows_last(const RowsLog L, const uint32_t *pos, uint32_t m,
+                                                           const RowsWork W) {
+    __shared__ unsigned int s_ok[kRowsWaves], s_ref[kRowsWaves];
+    const uint64_t tiles = rows_tiles(m);
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t j = t * kRowsBlock + threadIdx.x;
+        bool last = false;
+        if (j < m) {
+            last = true;
+            if (j + 1 < m) {
+                const uint32_t p = pos[j], q = pos[j + 1];
+                last = L.id[p] != L.id[q] || L.epoch[p] != L.epoch[q] || L.lec[p] != L.lec[q];
+            }
+            W.flag[j] = last ? 1 : 0;
+        }
+        rows_tile_count(last, false, W.cnt, tiles, t, s_ok, s_ref);
+    }
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_gather(const RowsLog L, const uint32_t *pos, uint32_t m,
+                                                             const RowsWork W, unsigned long long *out_lec,
+                                                             long long *out_epoch, long long *out_id,
+                                                             uint8_t *out_valid) {
+    __shared__ unsigned int s_ok[kRowsWaves];
+    const uint64_t tiles = rows_tiles(m);
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t j = t * kRowsBlock + threadIdx.x;
+        const bool ok = j < m && W.flag[j] == 1;
+        const uint32_t rank = rows_tile_rank(ok, s_ok);
+        if (!ok) continue;
+        const uint32_t p = pos[j];
+        const uint64_t o = uint64_t(W.cnt[4 + t]) + rank;
+        out_lec[o] = L.lec[p];
+        out_epoch[o] = L.epoch[p];
+        out_id[o] = L.id[p];
+        out_valid[o] = L.valid[p];
+    }
+}
+
+unsigned rows_grid(uint64_t n, unsigned grid, int cus) {
+    const uint64_t want = rows_tiles(n);
+    uint64_t most = grid ? grid : uint64_t(cus) * 8;
+    if (most > kRowsMaxGrid) most = kRowsMaxGrid;
+    return unsigned(want < most ? want : most);
+}
+
+hipError_t rows_scan(uint32_t *cnt, uint64_t n, hipStream_t st) {
+    hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(kRowsScanBlock), 0, st, cnt, rows_tiles(n));
+    return hipGetLastError();
+}
+
+template <int kKind>
+hipError_t rows_append_kind(const RowsLog &L, const RowsItems &I, const RowsWork &W, unsigned g, hipStream_t st) {
+    hipLaunchKernelGGL(k_rows_flag<kKind>, dim3(g), dim3(kRowsBlock), 0, st, I, W);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = rows_scan(W.cnt, I.n, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rows_place<kKind>, dim3(g), dim3(kRowsBlock), 0, st, L, I, W);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rows_end, dim3(1), dim3(64), 0, st, L, (const uint32_t *)W.cnt);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_rows_append(const RowsLog &L, const RowsItems &I, const RowsWork &W, unsigned grid, int cus,
+                              hipStream_t st) {
+    if (I.n == 0) return hipSuccess;
+    const unsigned g = rows_grid(I.n, grid, cus);
+    switch (I.kind) {
+    case 0: return rows_append_kind<0>(L, I, W, g, st);
+    case 1: return rows_append_kind<1>(L, I, W, g, st);
+    case 2: return rows_append_kind<2>(L, I, W, g, st);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_rows_match(const RowsLog &L, uint32_t m, bool by_lec, unsigned long long digest, long long since,
+                             long long until, const RowsWork &W, uint32_t *pos_out, unsigned grid, int cus,
+                             hipStream_t st) {
+    if (m == 0) return hipSuccess;
+    const unsigned g = rows_grid(m, grid, cus);
+    hipLaunchKernelGGL(k_rows_match, dim3(g), dim3(kRowsBlock), 0, st, L, m, by_lec ? 1 : 0, digest, since, until, W);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = rows_scan(W.cnt, m, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rows_positions, dim3(g), dim3(kRowsBlock), 0, st, m, W, pos_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_keys(const RowsLog &L, const uint32_t *pos, uint32_t m, int col, unsigned long long *key_out,
+                            unsigned grid, int cus, hipStream_t st) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rows_keys, dim3(rows_grid(m, grid, cus)), dim3(kRowsBlock), 0, st, L, pos, m, col, key_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_last(const RowsLog &L, const uint32_t *pos, uint32_t m, const RowsWork &W, unsigned grid,
+                            int cus, hipStream_t st) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rows_last, dim3(rows_grid(m, grid, cus)), dim3(kRowsBlock), 0, st, L, pos, m, W);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return rows_scan(W.cnt, m, st);
+}
+
+hipError_t launch_rows_gather(const RowsLog &L, const uint32_t *pos, uint32_t m, const RowsWork &W,
+                              unsigned long long *out_lec, long long *out_epoch, long long *out_id,
+                              uint8_t *out_valid, unsigned grid, int cus, hipStream_t st) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rows_gather, dim3(rows_grid(m, grid, cus)), dim3(kRowsBlock), 0, st, L, pos, m, W, out_lec,
+                       out_epoch, out_id, out_valid);
+    return hipGetLastError();
+}
+
+}  // namespace ske

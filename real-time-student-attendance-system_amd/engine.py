@@ -14,7 +14,8 @@ import gc
 import numpy as np
 
 from ._lib import (CmsInfo, Context, GenParams, HhInfo, HhStats, IngestDense, SKE_HH_ID_BYTES, SKE_HLL_DUMP_CARD,
-                   SKE_MEM_DEVICE, SKE_MEM_HOST, SKE_TALLY_KEY_BYTES, SKE_TP_BINS, SeenInfo, TallyInfo)
+                   SKE_MEM_DEVICE, SKE_MEM_HOST, SKE_TALLY_KEY_BYTES, SKE_TP_BINS, RowsInfo, SeenInfo, SKE_EROWSSPACE,
+                   SketchLibError, TallyInfo)
 from . import synthetic
 
 PASS_KINDS = 9  # SKE_PASS_KINDS (include/sketch.h)
@@ -241,6 +242,58 @@ def seen_test_keys(ctx: Context, sid: int, keys: np.ndarray) -> np.ndarray:
         ctx.call("ske_seen_test", int(sid), k.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p),
                  SKE_MEM_HOST)
     return out.astype(bool)
+
+
+def rows_info(ctx: Context, rid: int) -> dict:
+    """ske_rows_info: capacity, used, the rows taken, the refused ids among
+    them, the rows dropped at a full log and the sticky overflow word."""
+    info = RowsInfo()
+    ctx.call("ske_rows_info", int(rid), C.byref(info))
+    return {k: int(getattr(info, k)) for k, _ in RowsInfo._fields_}
+
+
+def rows_read(ctx: Context, rid: int, first: int, n: int):
+    """ske_rows_read: the raw log columns of positions ``[first, first + n)``:
+    ``(lecture digests u64, epochs i64, ids i64, valid u8)``."""
+    n = int(n)
+    lec, ep, ids, valid = np.zeros(n, np.uint64), np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.uint8)
+    if n:
+        ctx.call("ske_rows_read", int(rid), int(first), n, lec.ctypes.data_as(C.c_void_p),
+                 ep.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), valid.ctypes.data_as(C.c_void_p))
+    return lec, ep, ids, valid
+
+
+def rows_select(ctx: Context, rid: int, lecture: bytes | None, since: int, until: int, cols=None):
+    """ske_rows_select to host arrays: ``(cols, n, complete)``, ``cols`` the
+    four columns of which the first ``n`` entries are the answer.  ``cols``
+    given: a previous call's arrays, reused while they are large enough;
+    otherwise (or when they are too small) the count is asked for first
+    (``cap = 0``) and arrays of that size are made."""
+    n_out, complete = C.c_uint64(), C.c_int()
+    lec = None if lecture is None else C.c_char_p(lecture)
+    llen = 0 if lecture is None else len(lecture)
+
+    def call(cols, cap) -> bool:
+        """False: the rows do not fit ``cap`` (n_out says how many there are)."""
+        ptrs = [None] * 4 if cap == 0 else [c.ctypes.data_as(C.c_void_p) for c in cols]
+        try:
+            ctx.call("ske_rows_select", int(rid), lec, llen, int(since), int(until), *ptrs, cap, C.byref(n_out),
+                     C.byref(complete), SKE_MEM_HOST)
+        except SketchLibError as e:
+            if e.code != SKE_EROWSSPACE:
+                raise
+            return False
+        return int(n_out.value) <= cap
+
+    cap = 0 if cols is None else int(cols[0].size)
+    if not call(cols, cap):
+        cap = int(n_out.value)
+        cols = (np.zeros(cap, np.uint64), np.zeros(cap, np.int64), np.zeros(cap, np.int64), np.zeros(cap, np.uint8))
+        if not call(cols, cap):
+            raise SketchLibError(SKE_EROWSSPACE, "ERR row log selection does not fit the output")
+    if cols is None:
+        cols = (np.zeros(0, np.uint64), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.uint8))
+    return cols, int(n_out.value), bool(complete.value)
 
 
 class SweBatch(C.Structure):
@@ -646,6 +699,40 @@ class SketchEngine:
 
     def seen_test(self, sid: int, keys: DeviceBuffer, n: int, out: DeviceBuffer):
         self.ctx.call("ske_seen_test_async", int(sid), C.c_void_p(keys.ptr), int(n), C.c_void_p(out.ptr))
+
+    # ---- row logs (the attendance rows in arrival order)
+    def rows_init(self, rid: int, capacity_log2: int):
+        self.ctx.call("ske_rows_init", int(rid), int(capacity_log2))
+
+    def rows_free(self, rid: int):
+        self.ctx.call("ske_rows_free", int(rid))
+
+    def rows_reset(self, rid: int):
+        self.ctx.call("ske_rows_reset", int(rid))
+
+    def rows_info(self, rid: int) -> dict:
+        return rows_info(self.ctx, rid)
+
+    def rows_append_packed(self, rid: int, lec: DeviceBatch, ids: DeviceBatch, epoch: DeviceBuffer,
+                           valid: DeviceBuffer | None = None, mask: DeviceBuffer | None = None):
+        """ske_rows_append_fixed_async for fixed-width ids, else
+        ske_rows_append_packed_async, over resident columns (only enqueued, capturable)."""
+        vp = C.c_void_p(valid.ptr) if valid is not None else None
+        mp = C.c_void_p(mask.ptr) if mask is not None else None
+        if ids.width:
+            self.ctx.call("ske_rows_append_fixed_async", int(rid), C.c_void_p(lec.bytes.ptr), C.c_void_p(lec.offs.ptr),
+                          C.c_void_p(ids.bytes.ptr), ids.width, C.c_void_p(epoch.ptr), vp, mp, ids.n)
+        else:
+            self.ctx.call("ske_rows_append_packed_async", int(rid), C.c_void_p(lec.bytes.ptr),
+                          C.c_void_p(lec.offs.ptr), C.c_void_p(ids.bytes.ptr), C.c_void_p(ids.offs.ptr),
+                          C.c_void_p(epoch.ptr), vp, mp, ids.n)
+
+    def rows_select(self, rid: int, lecture: bytes | None = None, since: int = -(1 << 63),
+                    until: int = (1 << 63) - 1):
+        return rows_select(self.ctx, rid, lecture, since, until)
+
+    def rows_read(self, rid: int, first: int, n: int):
+        return rows_read(self.ctx, rid, first, n)
 
     # ---- ingest: the decoded messages' times, and the decoded messages as one packed batch
     def ingest_times(self, msgs: DeviceBuffer, cols, n: int, epoch: DeviceBuffer):

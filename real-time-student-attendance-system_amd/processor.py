@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import json
 import logging
-from datetime import datetime
+from datetime import datetime, timedelta
 from typing import Iterable, Sequence
 
 import numpy as np
@@ -172,7 +172,7 @@ class AttendanceProcessor:
         if batch:
             yield self.process_batch(batch)
 
-    # attendance_processor.py:149-165 (the Cassandra half is out of scope)
+    # attendance_processor.py:149-165 (the Cassandra half: counts' row log, when it keeps one)
     def get_attendance_stats(self, lecture_id: str, day: str | None = None) -> dict:
         """PFCOUNT of the lecture's key (:151-152).  In the README key form a
         lecture is counted per day: with a day, that day's key; without one
@@ -187,8 +187,16 @@ class AttendanceProcessor:
         rows valid or not and the invalid ones, over every day.  When ``counts``
         keeps a seen-row set (``dedup``) those are distinct rows, and
         ``duplicate_record_count`` is how many redelivered rows, of any
-        lecture, the set kept out of the counts."""
+        lecture, the set kept out of the counts.  When ``counts`` keeps a row
+        log (``records``) the dict carries ``attendance_records`` too, the
+        reference's ``SELECT student_id, timestamp`` (:154-165): the lecture's
+        rows as ``{"student_id", "timestamp"}`` in (timestamp, student_id)
+        order, each row once, timestamps as naive UTC datetimes of whole seconds."""
         out = {"unique_attendees": self._unique_attendees(lecture_id, day)}
+        if getattr(self.counts, "keeps_records", False):
+            rec = self.counts.records(lecture_id)
+            out["attendance_records"] = [{"student_id": int(i), "timestamp": _utc(int(e))}
+                                         for i, e in zip(rec["student_id"], rec["epoch"])]
         if getattr(self.counts, "counts_lectures", False):
             # the reference's attendance_records (:154-165), rows per lecture over
             # every day: the tally is keyed by lecture alone
@@ -198,6 +206,25 @@ class AttendanceProcessor:
         if getattr(self.counts, "dedup", False):
             out["duplicate_record_count"] = self.counts.duplicate_rows()
         return out
+
+    def fetch_attendance_data(self) -> list[dict]:
+        """attendance_analysis.py:19-52, the whole table as its ``all_records``
+        dicts (``student_id``, ``lecture_id``, ``timestamp``, ``is_valid``), each
+        row once with its last write, partitions in digest order and rows in
+        (timestamp, student_id) order inside one.  The log holds lecture
+        digests; the names come from the lecture tally's listing, so ``counts``
+        needs both ``records`` and ``lecture_counts`` (ValueError otherwise)."""
+        if not getattr(self.counts, "keeps_records", False):
+            raise ValueError("fetch_attendance_data needs a StudentCounts with records")
+        if not getattr(self.counts, "counts_lectures", False):
+            raise ValueError("fetch_attendance_data needs a StudentCounts with lecture_counts (the lecture names)")
+        from .client_rows import lecture_digest
+        names, *_ = self.redis_client.tally_list(self.counts._lectures)
+        by_digest = {lecture_digest(k): k.decode("utf-8", "replace") for k in names}
+        rec = self.counts.records()
+        return [{"student_id": int(i), "lecture_id": by_digest.get(int(d)), "timestamp": _utc(int(e)),
+                 "is_valid": bool(v)}
+                for d, e, i, v in zip(rec["lecture_digest"], rec["epoch"], rec["student_id"], rec["is_valid"])]
 
     def _unique_attendees(self, lecture_id: str, day: str | None) -> int:
         prefix = self.config.hll_key_prefix
@@ -215,6 +242,14 @@ class AttendanceProcessor:
             keys = list(self.redis_client.scan_iter(match=pat + ":" + "[0-9]" * 4 + "-" + "[0-9]" * 2 + "-" +
                                                      "[0-9]" * 2, _type="string"))
         return self.redis_client.pfcount(*keys) if keys else 0
+
+
+_EPOCH = datetime(1970, 1, 1)
+
+
+def _utc(seconds: int) -> datetime:
+    """Seconds since 1970-01-01T00:00:00 UTC as a naive UTC datetime."""
+    return _EPOCH + timedelta(seconds=seconds)
 
 
 def glob_escape(text: str) -> str:
