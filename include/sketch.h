@@ -92,7 +92,7 @@ extern "C" {
 #define SKE_EROWSNOLOG -42   /* row log id not in use */
 #define SKE_EROWSEXISTS -43  /* ske_rows_init on an id in use */
 #define SKE_EROWSCAP -44     /* capacity_log2 outside [SKE_ROWS_MIN_LOG2, SKE_ROWS_MAX_LOG2] */
-#define SKE_EROWSSPACE -45   /* ske_rows_select: more rows pass than the output arrays hold */
+#define SKE_EROWSSPACE -45   /* ske_rows_select / ske_rows_group: more rows (groups) pass than the output arrays hold */
 
 #define SKE_MEM_HOST 0
 #define SKE_MEM_DEVICE 1
@@ -132,6 +132,11 @@ extern "C" {
 #define SKE_ROWS_MAX_LOG2 28   /* a position fits a u32 */
 #define SKE_ROWS_BLOCK 256     /* items per workgroup and tile of an append: positions are tile prefix + rank */
 #define SKE_ROWS_ROW_BYTES 25  /* lec 8, epoch 8, id 8, valid 1 */
+#define SKE_ROWS_BY_STUDENT 0   /* ske_rows_group: key = id, groups ascending, signed */
+#define SKE_ROWS_BY_LECTURE 1   /*   key = lecture digest, groups ascending, unsigned */
+#define SKE_ROWS_VALID_ANY 0    /* ske_rows_group / ske_rows_profile: rows of either validity count, */
+#define SKE_ROWS_VALID_ONLY 1   /*   rows with is_valid 1, */
+#define SKE_ROWS_INVALID_ONLY 2 /*   rows with is_valid 0 */
 #define SKE_HLL_REGISTERS 16384
 #define SKE_HLL_DENSE_BYTES 12288
 #define SKE_HLL_DUMP_MAX_KEYS (1u << 18)   /* 2^18 * 12304 B < 2^32: u32 offsets suffice */
@@ -823,6 +828,48 @@ int ske_rows_select(ske_ctx *ctx, uint32_t rid, const uint8_t *lec_bytes_or_null
  * SKE_EINVAL when first + n passes `used`. */
 int ske_rows_read(ske_ctx *ctx, uint32_t rid, uint64_t first, uint64_t n, uint64_t *out_lec, int64_t *out_epoch,
                   int64_t *out_id, uint8_t *out_valid);
+
+/* Group-by.  The reference's analysis is five groupby(...).size() calls over
+ * the de-duplicated table (attendance_analysis.py:65-118); these two calls give
+ * them exactly, and only the groups leave the device.  The lecture and the
+ * [since, until) window are ske_rows_select's and the upsert collapse runs
+ * first: the validity filter, the sod_from filter and the count look at each
+ * run's surviving (last-appended) row only.  A survivor is counted when it
+ * passes valid_filter (SKE_ROWS_VALID_*) and its floored UTC second of the day
+ * is at least sod_from (0: no filter; above 86399: SKE_EINVAL).
+ *
+ * ske_rows_group: out_key[g], out_count[g] = the groups that have at least one
+ * counted row, ascending by key (pandas' group order; a group whose rows are all
+ * filtered out does not appear, as in df[mask].groupby().size()).  by =
+ * SKE_ROWS_BY_LECTURE: the key is the digest, compared unsigned; by =
+ * SKE_ROWS_BY_STUDENT: the id's two's-complement bits, the order signed.
+ * *n_out (= stats->n), *stats and *complete are always written.  More groups
+ * than cap: SKE_EROWSSPACE with no output array touched, so cap = 0 (both arrays
+ * may be NULL then) is the statistics alone; it succeeds when no group is
+ * listed.  mem says where the two output arrays are.  An unknown by or
+ * valid_filter is SKE_EINVAL.  Integer arithmetic throughout: the answer is the
+ * same from run to run.
+ *
+ * ske_rows_profile: out_bins[weekday * 24 + hour] (SKE_TP_BINS host words,
+ * Monday first, UTC, the time profile's layout) = the counted rows by their
+ * epoch's bin; *rows_out = the rows after the collapse.
+ *
+ * Both wait for the stream: SKE_EBUSY while a capture records. */
+typedef struct {
+    uint64_t rows;      /* rows in the window after the upsert collapse (what ske_rows_select would return) */
+    uint64_t n;         /* groups with at least one counted row */
+    uint64_t sum;       /* counted rows = sum of the counts */
+    uint64_t sumsq;     /* sum of count^2 (sum <= 2^28, so it fits) */
+    uint64_t min, max;  /* of the counts; 0, 0 when n == 0 */
+    uint64_t med_lo, med_hi; /* counts of 0-based rank (n-1)/2 and n/2 in ascending order; 0, 0 when n == 0 */
+} ske_rows_group_stats_t;
+int ske_rows_group(ske_ctx *ctx, uint32_t rid, int by, const uint8_t *lec_bytes_or_null, uint32_t lec_len,
+                   int64_t since, int64_t until, int valid_filter, uint32_t sod_from, uint64_t *out_key,
+                   uint64_t *out_count, uint64_t cap, uint64_t *n_out, ske_rows_group_stats_t *stats, int *complete,
+                   int mem);
+int ske_rows_profile(ske_ctx *ctx, uint32_t rid, const uint8_t *lec_bytes_or_null, uint32_t lec_len, int64_t since,
+                     int64_t until, int valid_filter, uint32_t sod_from, uint64_t *out_bins, uint64_t *rows_out,
+                     int *complete);
 
 /* ---- the fused hot path (K1) ----
  * For every swipe i: v = BF.EXISTS fid id_i; if v: PFADD slot_i id_i.

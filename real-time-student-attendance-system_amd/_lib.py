@@ -91,6 +91,8 @@ SKE_ROWS_MIN_LOG2 = 8
 SKE_ROWS_MAX_LOG2 = 28
 SKE_ROWS_BLOCK = 256
 SKE_ROWS_ROW_BYTES = 25
+SKE_ROWS_BY_STUDENT, SKE_ROWS_BY_LECTURE = 0, 1
+SKE_ROWS_VALID_ANY, SKE_ROWS_VALID_ONLY, SKE_ROWS_INVALID_ONLY = 0, 1, 2
 HLL_REGISTERS = 16384
 HLL_DENSE_BYTES = 12288
 SKE_HLL_DUMP_MAX_KEYS = 1 << 18
@@ -148,6 +150,12 @@ class RowsInfo(C.Structure):
     """ske_rows_info_t (include/sketch.h)."""
     _fields_ = [("capacity", C.c_uint64), ("used", C.c_uint64), ("taken", C.c_uint64),
                 ("refused_ids", C.c_uint64), ("dropped", C.c_uint64), ("overflow", C.c_uint64)]
+
+
+class RowsGroupStats(C.Structure):
+    """ske_rows_group_stats_t (include/sketch.h)."""
+    _fields_ = [("rows", C.c_uint64), ("n", C.c_uint64), ("sum", C.c_uint64), ("sumsq", C.c_uint64),
+                ("min", C.c_uint64), ("max", C.c_uint64), ("med_lo", C.c_uint64), ("med_hi", C.c_uint64)]
 
 
 class IngestCols(C.Structure):
@@ -299,6 +307,11 @@ SIGNATURES = {
                                   C.c_int]),
     "ske_rows_select": (C.c_int, [_CTX, C.c_uint32, _u8p, C.c_uint32, C.c_int64, C.c_int64, _u64p, _vp, _vp, _u8p,
                                   C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_int]),
+    "ske_rows_group": (C.c_int, [_CTX, C.c_uint32, C.c_int, _u8p, C.c_uint32, C.c_int64, C.c_int64, C.c_int,
+                                 C.c_uint32, _u64p, _u64p, C.c_uint64, C.POINTER(C.c_uint64),
+                                 C.POINTER(RowsGroupStats), C.POINTER(C.c_int), C.c_int]),
+    "ske_rows_profile": (C.c_int, [_CTX, C.c_uint32, _u8p, C.c_uint32, C.c_int64, C.c_int64, C.c_int, C.c_uint32,
+                                   _u64p, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "ske_rows_read": (C.c_int, [_CTX, C.c_uint32, C.c_uint64, C.c_uint64, _u64p, _vp, _vp, _u8p]),
     "ske_swipes": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p, C.c_int]),
     "ske_swipes_async": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p]),

@@ -39,7 +39,9 @@ That table's rows have a counterpart too.  With ``records`` set, a row log
 (client_rows.py, DESIGN.md "Row log") keeps every row the counting calls are
 given -- (lecture, time, student id, is_valid), in arrival order, on the
 device -- and ``records`` reads a lecture's rows back in the table's order,
-each row once with its last write.
+each row once with its last write.  Over those rows ``exact_insights`` runs the
+reference's five group-bys themselves on the device (DESIGN.md "Row log
+group-by"): no estimate, no track threshold, repeats collapsed by the log.
 """
 from __future__ import annotations
 
@@ -395,6 +397,90 @@ class StudentCounts:
         lo = None if since is None else int(epoch_seconds([since])[0])
         hi = None if until is None else int(epoch_seconds([until])[0])
         return self.client.rows_select(self._records, lecture, lo, hi)
+
+    _EXACT = {"attended": dict(), "late": dict(late=True), "invalid": dict(valid=False)}
+
+    def exact_counts(self, which: str, groups: bool = True) -> dict:
+        """``client.rows_group`` by student over the whole log -- the
+        reference's per-student ``groupby('student_id').size()``, exact, each
+        row once with its last write: ``which`` "attended" counts every row,
+        valid or not, as the reference's consistency insight does
+        (attendance_analysis.py:100); "late" the rows whose UTC second of the
+        day is at least ``late_from`` (:68); "invalid" the rows with
+        ``is_valid`` false (:112).  ``{"keys", "counts", "stats", "complete"}``."""
+        if self._records is None:
+            raise ValueError("no records")
+        if which not in self._EXACT:
+            raise ValueError('which is "attended", "invalid" or "late"')
+        opt = self._EXACT[which]
+        return self.client.rows_group(self._records, "student", valid=opt.get("valid"),
+                                      late_from=self.late_from if opt.get("late") else None, groups=groups)
+
+    def exact_by_day(self) -> dict:
+        """``by_day`` from the log's rows (``client.rows_profile``): ``{day
+        name: rows}`` of the weekdays that have any, in the order of the names."""
+        if self._records is None:
+            raise ValueError("no records")
+        per_day = self.client.rows_profile(self._records).sum(axis=1)
+        return {d: int(per_day[i]) for d, i in sorted((d, i) for i, d in enumerate(DAY_NAMES)) if per_day[i]}
+
+    def exact_lecture_rankings(self, k: int = 3) -> dict:
+        """``lecture_rankings`` from the log's rows: ``client.rows_group`` by
+        lecture, the digests joined to names through the tally's listing (as
+        ``AttendanceProcessor.fetch_attendance_data`` does; a digest the listing
+        does not name shows as ``"#<hex digest>"``), in ``lecture_rankings``'
+        total order -- count descending, name ascending."""
+        if self._records is None:
+            raise ValueError("no records")
+        if self._lectures is None:
+            raise ValueError("exact_lecture_rankings needs lecture_counts (the lecture names)")
+        from .client_rows import lecture_digest
+        names, *_ = self.client.tally_list(self._lectures)
+        by_digest = {lecture_digest(key): key.decode("utf-8", "replace") for key in names}
+        g = self.client.rows_group(self._records, "lecture")
+        ranked = sorted((-int(c), by_digest.get(int(d), "#%016x" % int(d))) for d, c in zip(g["keys"], g["counts"]))
+        k = int(k)
+        return {"most_attended": {name: -c for c, name in ranked[:k]},
+                "least_attended": {name: -c for c, name in ranked[max(len(ranked) - k, 0):]} if k > 0 else {},
+                "complete": g["complete"]}
+
+    def exact_insights(self, lecture_k: int | None = 3) -> list:
+        """The reference's five insights (attendance_analysis.py:65-118) in its
+        order, exact: each a group-by over the log's rows after the upsert,
+        computed on the device; only the groups come to the host.  Titles and
+        descriptions as ``insights`` writes them; ``data`` is ``{int
+        student_id: count}``, ``{day name: count}`` by day.  Latecomers pass
+        ``count > median`` (``2 * count > med_lo + med_hi``), consistent
+        attendees ``count > median + std`` (``reference_rule``, in integers);
+        every entry carries the log's ``complete``.  ``lecture_k=None`` leaves
+        the lecture entry out (it needs ``lecture_counts``)."""
+        late = self.exact_counts("late")
+        twice = late["stats"]["med_lo"] + late["stats"]["med_hi"]
+        data = {int(i): int(c) for i, c in zip(late["keys"], late["counts"]) if 2 * int(c) > twice}
+        out = [{"title": "Habitual Latecomers",
+                "description": f"Found {len(data)} students who frequently arrive after "
+                               f"{self.late_from // 3600}:00 AM",
+                "data": data, "complete": late["complete"]},
+               {"title": "Attendance by Day", "description": "Distribution of attendance across different days",
+                "data": self.exact_by_day(), "complete": late["complete"]}]
+        if lecture_k is not None:
+            ranks = self.exact_lecture_rankings(lecture_k)
+            out.append({"title": "Lecture Attendance Rankings", "description": "Most and least attended lectures",
+                        "data": {"most_attended": ranks["most_attended"], "least_attended": ranks["least_attended"]},
+                        "complete": ranks["complete"]})
+        att = self.exact_counts("attended")
+        thr = reference_rule(att["stats"], "median+std")
+        out.append({"title": "Most Consistent Attendees",
+                    "description": "Students whose estimated attendance reaches the threshold",
+                    "data": {int(i): int(c) for i, c in zip(att["keys"], att["counts"])
+                             if thr is not None and int(c) >= thr},
+                    "complete": att["complete"]})
+        inv = self.exact_counts("invalid")
+        out.append({"title": "Invalid Attendance Attempts",
+                    "description": "Estimated invalid attendance attempts by student id",
+                    "data": {int(i): int(c) for i, c in zip(inv["keys"], inv["counts"])},
+                    "complete": inv["complete"]})
+        return out
 
     def records_info(self) -> dict:
         """``client.rows_info`` of the log: capacity, used, taken, refused_ids,

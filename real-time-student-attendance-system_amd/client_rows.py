@@ -11,7 +11,12 @@ log exists it makes no further native call.
 A row's partition is its lecture's digest (``lecture_digest``), its id an
 integer: the id column of an append is canonical decimal text (``parse_id``),
 anything else is refused and counted.  ``rows_oracle`` restates the whole
-pipeline in Python and is the oracle of the device's answers."""
+pipeline in Python and is the oracle of the device's answers.
+
+``rows_group`` and ``rows_profile`` count the log's rows after the upsert by
+student, by lecture or by weekday and hour, on the device -- the reference's
+``groupby(...).size()`` calls (attendance_analysis.py:65-118), exact;
+``rows_group_oracle`` and ``rows_profile_oracle`` are their oracles."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from .encoding import encode, pack
-from .engine import DeviceBuffer, rows_info, rows_read, rows_select
+from .engine import DeviceBuffer, rows_group, rows_info, rows_profile, rows_read, rows_select
 from .exceptions import ResponseError
 from .keyhash import murmur64a
 
@@ -102,6 +107,61 @@ def rows_oracle(batches, lecture=None, since=None, until=None, capacity=None) ->
                 np.asarray([r[2] for r in rows], np.int64), np.asarray([r[3] for r in rows], np.uint8))
 
     return {"log": cols(log), "taken": taken, "refused_ids": refused, "dropped": dropped, "select": cols(sel)}
+
+
+def _counted(rows, valid, late_from):
+    """The selected rows that count: ``valid`` None / True / False keeps either
+    validity / the valid / the invalid rows, ``late_from`` (None: 0) those whose
+    floored UTC second of the day is at least it."""
+    lec, ep, ids, ok = rows
+    keep = np.ones(ep.size, bool)
+    if valid is not None:
+        keep &= (ok != 0) == bool(valid)
+    if late_from:
+        keep &= np.asarray([int(e) % 86400 >= int(late_from) for e in ep.tolist()], bool)
+    return lec[keep], ep[keep], ids[keep]
+
+
+def group_stats(counts) -> dict:
+    """``n``, ``sum``, ``sumsq``, ``min``, ``max``, ``med_lo``, ``med_hi`` and
+    ``median`` of a list of counts, in Python ints (``median`` exact: a half is
+    a float's to hold)."""
+    c = sorted(int(x) for x in counts)
+    n = len(c)
+    lo, hi = (c[(n - 1) // 2], c[n // 2]) if n else (0, 0)
+    return {"n": n, "sum": sum(c), "sumsq": sum(x * x for x in c), "min": c[0] if n else 0, "max": c[-1] if n else 0,
+            "med_lo": lo, "med_hi": hi, "median": (lo + hi) / 2}
+
+
+def rows_group_oracle(batches, by="student", lecture=None, since=None, until=None, valid=None, late_from=None,
+                      capacity=None) -> dict:
+    """``RowsMixin.rows_group`` in pure Python on top of ``rows_oracle``: the
+    rows after the upsert, those that count (``_counted``), grouped by student
+    id (int64, ascending signed) or lecture digest (uint64, ascending)."""
+    if by not in ("student", "lecture"):
+        raise ValueError('by is "student" or "lecture"')
+    sel = rows_oracle(batches, lecture, since, until, capacity)["select"]
+    lec, ep, ids = _counted(sel, valid, late_from)
+    col = ids.tolist() if by == "student" else lec.tolist()
+    groups: dict[int, int] = {}
+    for k in col:
+        groups[k] = groups.get(k, 0) + 1
+    keys = sorted(groups)
+    stats = group_stats(groups.values())
+    stats["rows"] = int(sel[1].size)
+    return {"keys": np.asarray(keys, np.int64 if by == "student" else np.uint64),
+            "counts": np.asarray([groups[k] for k in keys], np.uint64), "stats": stats}
+
+
+def rows_profile_oracle(batches, lecture=None, since=None, until=None, valid=None, late_from=None,
+                        capacity=None) -> np.ndarray:
+    """``RowsMixin.rows_profile`` in pure Python: the counted rows per weekday
+    (Monday first; 1970-01-01 was a Thursday) and UTC hour, by floor division."""
+    sel = rows_oracle(batches, lecture, since, until, capacity)["select"]
+    out = np.zeros((7, 24), np.uint64)
+    for e in _counted(sel, valid, late_from)[1].tolist():
+        out[(e // 86400 + 3) % 7, e % 86400 // 3600] += 1
+    return out
 
 
 class RowsMixin:
@@ -244,3 +304,46 @@ class RowsMixin:
         used = rows_info(self.ctx, rid)["used"]
         lec, ep, ids, valid = rows_read(self.ctx, rid, 0, used)
         return {"lecture_digest": lec, "epoch": ep, "student_id": ids, "is_valid": valid}
+
+    @staticmethod
+    def _rows_window(lecture, since, until, valid, late_from):
+        lec = None if lecture is None else _lecture_bytes(lecture)
+        lo = INT64_MIN if since is None else int(since)
+        hi = INT64_MAX if until is None else int(until)
+        vf = _lib.SKE_ROWS_VALID_ANY if valid is None else (_lib.SKE_ROWS_VALID_ONLY if valid
+                                                            else _lib.SKE_ROWS_INVALID_ONLY)
+        sod = 0 if late_from is None else int(late_from)
+        if not 0 <= sod <= 86399:
+            raise ValueError("late_from is a second of the day, 0 to 86399")
+        return lec, lo, hi, vf, sod
+
+    def rows_group(self, name, by="student", lecture=None, since=None, until=None, valid=None, late_from=None,
+                   groups: bool = True) -> dict:
+        """The log's rows after the upsert, counted per student or per lecture
+        on the device (``ske_rows_group``): ``{"keys", "counts", "stats",
+        "complete"}``.  The window is ``rows_select``'s; ``valid`` None / True /
+        False counts rows of either validity / the valid / the invalid ones,
+        ``late_from`` (None: no filter) those whose UTC second of the day is at
+        least it.  ``keys`` -- int64 student ids, ascending, or uint64 lecture
+        digests, ascending -- and ``counts`` (uint64) list the groups with at
+        least one counted row, as ``df[mask].groupby(col).size()`` does.
+        ``stats``: ``rows`` (the window's rows after the upsert), ``n``, ``sum``,
+        ``sumsq``, ``min``, ``max``, ``med_lo``, ``med_hi`` and ``median`` of the
+        counts, in the form ``analysis.reference_rule`` takes.  ``groups``
+        False: the statistics alone, ``keys`` and ``counts`` empty."""
+        if by not in ("student", "lecture"):
+            raise ValueError('by is "student" or "lecture"')
+        lec, lo, hi, vf, sod = self._rows_window(lecture, since, until, valid, late_from)
+        student = by == "student"
+        keys, counts, stats, complete = rows_group(
+            self.ctx, self.rows_rid(name), _lib.SKE_ROWS_BY_STUDENT if student else _lib.SKE_ROWS_BY_LECTURE, lec, lo,
+            hi, vf, sod, groups)
+        stats["median"] = (stats["med_lo"] + stats["med_hi"]) / 2
+        return {"keys": keys.view(np.int64).copy() if student else keys.copy(), "counts": counts.copy(),
+                "stats": stats, "complete": complete}
+
+    def rows_profile(self, name, lecture=None, since=None, until=None, valid=None, late_from=None) -> np.ndarray:
+        """The same counted rows per weekday (Monday first) and UTC hour
+        (``ske_rows_profile``): a ``[7, 24]`` uint64 array."""
+        lec, lo, hi, vf, sod = self._rows_window(lecture, since, until, valid, late_from)
+        return rows_profile(self.ctx, self.rows_rid(name), lec, lo, hi, vf, sod)[0]

@@ -1,7 +1,8 @@
 // sketch_api_rows.cpp -- libsketch C-ABI (include/sketch.h): row logs, the
 // attendance table's rows in arrival order (init, reset, info, the three
-// appends, select, read), kernels in sketch_rows.hip.  A log is one device
+// appends, select, group, profile, read), kernels in sketch_rows.hip.  A log is one device
 // allocation owned by the context and addressed by rid.
+#include <stddef.h>
 #include <string.h>
 
 #include "sketch_ctx.h"
@@ -15,6 +16,11 @@ static_assert(sizeof(ske_rows_info_t) == 48, "six u64 words");
 static_assert(SKE_EROWSNOLOG == -42 && SKE_EROWSEXISTS == -43 && SKE_EROWSCAP == -44 && SKE_EROWSSPACE == -45,
               "the row-log error codes");
 static_assert(SKE_ROWS_ROW_BYTES == 25, "three words and a byte");
+static_assert(SKE_ROWS_BY_STUDENT == kRowsByStudent && SKE_ROWS_BY_LECTURE == kRowsByLecture &&
+                  SKE_ROWS_VALID_ANY == kRowsValidAny && SKE_ROWS_VALID_ONLY == kRowsValidOnly &&
+                  SKE_ROWS_INVALID_ONLY == kRowsInvalidOnly,
+              "the group-by's selectors as sketch.h states them");
+static_assert(sizeof(ske_rows_group_stats_t) == 64 && SKE_TP_BINS == kTpBins, "eight u64 words; the profile's bins");
 
 namespace {
 
@@ -92,6 +98,96 @@ static int append_args(ske_ctx *c, uint32_t rid, uint64_t n, const int64_t *epoc
     if (n >= 0xffffffffull) return SKE_EINVAL;
     if (n && (!epoch || (reinterpret_cast<uintptr_t>(epoch) & 7))) return SKE_EINVAL;
     return SKE_OK;
+}
+
+// What the select, the group-by and the profile share (steps 1 to 4): the
+// window's positions, sorted with one stable pass per key column, and the flag
+// of each run's last-appended row.
+struct RowsFront {
+    uint32_t m;     // rows in the window before the collapse
+    uint32_t runs;  //   after it
+    uint32_t *pos;  // m positions in sorted order
+    RowsWork W;     // flag[j] = pos[j] survives; cnt: the flags' totals and scanned tile counts
+};
+
+// id_last: the id is the most significant column (epoch, lecture, id) -- the
+// rows lie grouped by id, ascending and signed; else the table's order (lecture,
+// epoch, id).  Equal (lecture, epoch, id) are adjacent either way, the
+// last-appended row last.  *complete is written; F->m == 0: nothing matches.
+static int rows_front(ske_ctx *c, const Rows &R, const uint8_t *lec_bytes, uint32_t lec_len, int64_t since,
+                      int64_t until, bool id_last, int *complete, RowsFront *F) {
+    RowsHead h{};
+    int rc = rows_head(c, R, &h);
+    if (rc) return rc;
+    *complete = h.overflow ? 0 : 1;
+    const uint32_t used = uint32_t(h.used);  // <= 2^28
+    if (used == 0) return SKE_OK;
+    const RowsLog L = log_of(R);
+    const bool by_lec = lec_bytes != nullptr || lec_len != 0;
+    if (lec_len && !lec_bytes) return SKE_EINVAL;
+    const unsigned long long digest = by_lec ? rows_lecture_digest(lec_bytes, lec_len) : 0;
+
+    hipError_t e = hipSuccess;
+    RowsWork W{};
+    W.flag = (uint8_t *)scratch_get(c->scratch, kScrRowsSelFlag, used, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    W.cnt = (uint32_t *)scratch_get(c->scratch, kScrRowsSelCnt, rows_cnt_bytes(used), &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    uint32_t *pos = (uint32_t *)scratch_get(c->scratch, kScrVals, uint64_t(used) * 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    const unsigned grid = unsigned(c->rows_grid);
+
+    // 1, 2: the matching positions, ascending
+    HIPCHK(c, launch_rows_match(L, used, by_lec, digest, since, until, W, pos, grid, c->cus, c->st));
+    uint32_t m = 0;
+    HIPCHK(c, hipMemcpyAsync(&m, W.cnt, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (m == 0) return SKE_OK;
+
+    // 3: one stable pass per column (0 id, 1 epoch, 2 lecture), the least significant first; one
+    // lecture's rows need no lecture pass
+    unsigned long long *keys = (unsigned long long *)scratch_get(c->scratch, kScrKeysOrFirst, uint64_t(m) * 8, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    unsigned long long *keys_s = (unsigned long long *)scratch_get(c->scratch, kScrKeysSorted, uint64_t(m) * 8, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    uint32_t *pos_s = (uint32_t *)scratch_get(c->scratch, kScrValsSorted, uint64_t(m) * 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    uint32_t *cur = pos, *nxt = pos_s;
+    int order[3], passes = 0;
+    if (id_last) {
+        order[passes++] = 1;
+        if (!by_lec) order[passes++] = 2;
+        order[passes++] = 0;
+    } else {
+        order[passes++] = 0;
+        order[passes++] = 1;
+        if (!by_lec) order[passes++] = 2;
+    }
+    for (int k = 0; k < passes; k++) {
+        const int col = order[k];
+        HIPCHK(c, launch_rows_keys(L, cur, m, col, keys, grid, c->cus, c->st));
+        e = rows_sort_pairs(c->scratch, col < 2, keys, keys_s, cur, nxt, m, c->st);
+        if (e == hipErrorStreamCaptureUnsupported) return scratch_error(c, e);
+        HIPCHK(c, e);
+        uint32_t *t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+
+    // 4: the last-appended row of each run of equal keys
+    HIPCHK(c, launch_rows_last(L, cur, m, W, grid, c->cus, c->st));
+    uint32_t runs = 0;
+    HIPCHK(c, hipMemcpyAsync(&runs, W.cnt, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    F->m = m;
+    F->runs = runs;
+    F->pos = cur;
+    F->W = W;
+    return SKE_OK;
+}
+
+static bool rows_filter_ok(int valid_filter, uint32_t sod_from) {
+    return valid_filter >= SKE_ROWS_VALID_ANY && valid_filter <= SKE_ROWS_INVALID_ONLY && sod_from <= kRowsSodMax;
 }
 
 extern "C" {
@@ -329,59 +425,13 @@ int ske_rows_select(ske_ctx *c, uint32_t rid, const uint8_t *lec_bytes, uint32_t
     Rows *R = rows_for_sync_call(c, rid, "ske_rows_select", &rc);
     if (!R) return rc;
     if (cap && (!out_lec || !out_epoch || !out_id || !out_valid)) return SKE_EINVAL;
-    RowsHead h{};
-    rc = rows_head(c, *R, &h);
-    if (rc) return rc;
     *n_out = 0;
-    *complete = h.overflow ? 0 : 1;
-    const uint32_t used = uint32_t(h.used);  // <= 2^28
-    if (used == 0) return SKE_OK;
+    RowsFront F{};
+    rc = rows_front(c, *R, lec_bytes, lec_len, since, until, false, complete, &F);
+    if (rc || F.m == 0) return rc;
+    const uint32_t runs = F.runs, m = F.m;
     const RowsLog L = log_of(*R);
-    const bool by_lec = lec_bytes != nullptr || lec_len != 0;
-    if (lec_len && !lec_bytes) return SKE_EINVAL;
-    const unsigned long long digest = by_lec ? rows_lecture_digest(lec_bytes, lec_len) : 0;
-
-    hipError_t e = hipSuccess;
-    RowsWork W{};
-    W.flag = (uint8_t *)scratch_get(c->scratch, kScrRowsSelFlag, used, &e);
-    if (e != hipSuccess) return scratch_error(c, e);
-    W.cnt = (uint32_t *)scratch_get(c->scratch, kScrRowsSelCnt, rows_cnt_bytes(used), &e);
-    if (e != hipSuccess) return scratch_error(c, e);
-    uint32_t *pos = (uint32_t *)scratch_get(c->scratch, kScrVals, uint64_t(used) * 4, &e);
-    if (e != hipSuccess) return scratch_error(c, e);
     const unsigned grid = unsigned(c->rows_grid);
-
-    // 1, 2: the matching positions, ascending
-    HIPCHK(c, launch_rows_match(L, used, by_lec, digest, since, until, W, pos, grid, c->cus, c->st));
-    uint32_t m = 0;
-    HIPCHK(c, hipMemcpyAsync(&m, W.cnt, 4, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (m == 0) return SKE_OK;
-
-    // 3: one stable pass per column, the least significant first
-    unsigned long long *keys = (unsigned long long *)scratch_get(c->scratch, kScrKeysOrFirst, uint64_t(m) * 8, &e);
-    if (e != hipSuccess) return scratch_error(c, e);
-    unsigned long long *keys_s = (unsigned long long *)scratch_get(c->scratch, kScrKeysSorted, uint64_t(m) * 8, &e);
-    if (e != hipSuccess) return scratch_error(c, e);
-    uint32_t *pos_s = (uint32_t *)scratch_get(c->scratch, kScrValsSorted, uint64_t(m) * 4, &e);
-    if (e != hipSuccess) return scratch_error(c, e);
-    uint32_t *cur = pos, *nxt = pos_s;
-    const int passes = by_lec ? 2 : 3;
-    for (int col = 0; col < passes; col++) {
-        HIPCHK(c, launch_rows_keys(L, cur, m, col, keys, grid, c->cus, c->st));
-        e = rows_sort_pairs(c->scratch, col < 2, keys, keys_s, cur, nxt, m, c->st);
-        if (e == hipErrorStreamCaptureUnsupported) return scratch_error(c, e);
-        HIPCHK(c, e);
-        uint32_t *t = cur;
-        cur = nxt;
-        nxt = t;
-    }
-
-    // 4: the last-appended row of each run of equal keys
-    HIPCHK(c, launch_rows_last(L, cur, m, W, grid, c->cus, c->st));
-    uint32_t runs = 0;
-    HIPCHK(c, hipMemcpyAsync(&runs, W.cnt, 4, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
     *n_out = runs;
     if (runs > cap) return SKE_EROWSSPACE;
 
@@ -399,14 +449,125 @@ int ske_rows_select(ske_ctx *c, uint32_t rid, const uint8_t *lec_bytes, uint32_t
         d_valid = (uint8_t *)stage_buf(c, kStgRowsValid, runs, &rc);
         if (rc) return rc;
     }
-    HIPCHK(c, launch_rows_gather(L, cur, m, W, (unsigned long long *)d_lec, (long long *)d_epoch, (long long *)d_id,
-                                 d_valid, grid, c->cus, c->st));
+    HIPCHK(c, launch_rows_gather(L, F.pos, m, F.W, (unsigned long long *)d_lec, (long long *)d_epoch,
+                                 (long long *)d_id, d_valid, grid, c->cus, c->st));
     if (mem != SKE_MEM_DEVICE) {
         HIPCHK(c, hipMemcpyAsync(out_lec, d_lec, uint64_t(runs) * 8, hipMemcpyDeviceToHost, c->st));
         HIPCHK(c, hipMemcpyAsync(out_epoch, d_epoch, uint64_t(runs) * 8, hipMemcpyDeviceToHost, c->st));
         HIPCHK(c, hipMemcpyAsync(out_id, d_id, uint64_t(runs) * 8, hipMemcpyDeviceToHost, c->st));
         HIPCHK(c, hipMemcpyAsync(out_valid, d_valid, runs, hipMemcpyDeviceToHost, c->st));
     }
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SKE_OK;
+}
+
+int ske_rows_group(ske_ctx *c, uint32_t rid, int by, const uint8_t *lec_bytes, uint32_t lec_len, int64_t since,
+                   int64_t until, int valid_filter, uint32_t sod_from, uint64_t *out_key, uint64_t *out_count,
+                   uint64_t cap, uint64_t *n_out, ske_rows_group_stats_t *stats, int *complete, int mem) {
+    if (!c || !n_out || !stats || !complete) return SKE_EINVAL;
+    *n_out = 0;
+    *complete = 1;
+    memset(stats, 0, sizeof *stats);
+    if (!rows_filter_ok(valid_filter, sod_from)) return SKE_EINVAL;
+    if (by != SKE_ROWS_BY_STUDENT && by != SKE_ROWS_BY_LECTURE) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Rows *R = rows_for_sync_call(c, rid, "ske_rows_group", &rc);
+    if (!R) return rc;
+    if (cap && (!out_key || !out_count)) return SKE_EINVAL;
+    RowsFront F{};
+    rc = rows_front(c, *R, lec_bytes, lec_len, since, until, by == SKE_ROWS_BY_STUDENT, complete, &F);
+    if (rc || F.m == 0) return rc;
+    stats->rows = F.runs;
+    const uint32_t m = F.m;
+    const RowsLog L = log_of(*R);
+    const unsigned grid = unsigned(c->rows_grid);
+
+    RowsGrpDev *D = (RowsGrpDev *)stage_buf(c, kStgRowsGrp, sizeof(RowsGrpDev), &rc);
+    if (rc) return rc;
+    hipError_t e = hipSuccess;
+    RowsGrpWork G{};
+    G.gflag = (uint8_t *)scratch_get(c->scratch, kScrRowsGrpFlag, m, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    // the three tile-count arrays side by side (the listed groups are at most m)
+    const size_t cb = (rows_cnt_bytes(m) + 15) & ~size_t(15);
+    uint8_t *cnts = (uint8_t *)scratch_get(c->scratch, kScrRowsGrpCnt, 3 * cb, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    G.cnt_c = (uint32_t *)cnts;
+    G.cnt_e = (uint32_t *)(cnts + cb);
+    G.cnt_l = (uint32_t *)(cnts + 2 * cb);
+    // the sort is over: its key buffers (m words each) hold the groups' keys
+    G.gkey = (unsigned long long *)scratch_get(c->scratch, kScrKeysOrFirst, uint64_t(m) * 8, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    G.lkey = (unsigned long long *)scratch_get(c->scratch, kScrKeysSorted, uint64_t(m) * 8, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    G.gend = (uint32_t *)scratch_get(c->scratch, kScrRowsGrpEnds, uint64_t(m) * 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    G.lcount = (uint32_t *)scratch_get(c->scratch, kScrRowsGrpCounts, uint64_t(m) * 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+
+    HIPCHK(c, launch_rows_grp_init(D, c->st));
+    HIPCHK(c, launch_rows_grp_flags(L, F.pos, m, by, valid_filter, sod_from, F.W, G, grid, c->cus, c->st));
+    uint32_t groups = 0;
+    HIPCHK(c, hipMemcpyAsync(&groups, G.cnt_e, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, launch_rows_grp_counts(G, groups, D, grid, c->cus, c->st));
+    RowsGrpDev h{};
+    const size_t head = offsetof(RowsGrpDev, hist);  // the accumulators and the select state
+    HIPCHK(c, hipMemcpyAsync(&h, D, head, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    const uint32_t n = uint32_t(h.n);  // <= m
+    if (n == 0) return SKE_OK;
+    HIPCHK(c, launch_rows_grp_median(G, n, D, grid, c->cus, c->st));
+    HIPCHK(c, hipMemcpyAsync(&h, D, head, hipMemcpyDeviceToHost, c->st));
+    const bool fits = n <= cap;
+    uint64_t *d_key = out_key, *d_count = out_count;
+    if (fits) {
+        if (mem != SKE_MEM_DEVICE) {
+            d_key = (uint64_t *)stage_buf(c, kStgRowsLec, uint64_t(n) * 8, &rc);
+            if (rc) return rc;
+            d_count = (uint64_t *)stage_buf(c, kStgRowsEpoch, uint64_t(n) * 8, &rc);
+            if (rc) return rc;
+        }
+        HIPCHK(c, launch_rows_grp_out(G, n, (unsigned long long *)d_key, (unsigned long long *)d_count, grid, c->cus,
+                                      c->st));
+        if (mem != SKE_MEM_DEVICE) {
+            HIPCHK(c, hipMemcpyAsync(out_key, d_key, uint64_t(n) * 8, hipMemcpyDeviceToHost, c->st));
+            HIPCHK(c, hipMemcpyAsync(out_count, d_count, uint64_t(n) * 8, hipMemcpyDeviceToHost, c->st));
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    *n_out = n;
+    stats->n = h.n;
+    stats->sum = h.sum;
+    stats->sumsq = h.sumsq;
+    stats->min = h.min;
+    stats->max = h.max;
+    stats->med_lo = h.sel.prefix[0];
+    stats->med_hi = h.sel.prefix[1];
+    return fits ? SKE_OK : SKE_EROWSSPACE;
+}
+
+int ske_rows_profile(ske_ctx *c, uint32_t rid, const uint8_t *lec_bytes, uint32_t lec_len, int64_t since,
+                     int64_t until, int valid_filter, uint32_t sod_from, uint64_t *out_bins, uint64_t *rows_out,
+                     int *complete) {
+    if (!c || !out_bins || !rows_out || !complete) return SKE_EINVAL;
+    *rows_out = 0;
+    *complete = 1;
+    memset(out_bins, 0, SKE_TP_BINS * sizeof(uint64_t));
+    if (!rows_filter_ok(valid_filter, sod_from)) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Rows *R = rows_for_sync_call(c, rid, "ske_rows_profile", &rc);
+    if (!R) return rc;
+    RowsFront F{};
+    rc = rows_front(c, *R, lec_bytes, lec_len, since, until, false, complete, &F);
+    if (rc || F.m == 0) return rc;
+    *rows_out = F.runs;
+    RowsGrpDev *D = (RowsGrpDev *)stage_buf(c, kStgRowsGrp, sizeof(RowsGrpDev), &rc);
+    if (rc) return rc;
+    HIPCHK(c, launch_rows_grp_init(D, c->st));
+    HIPCHK(c, launch_rows_profile(log_of(*R), F.pos, F.m, valid_filter, sod_from, F.W, D, unsigned(c->rows_grid),
+                                  c->cus, c->st));
+    HIPCHK(c, hipMemcpyAsync(out_bins, D->bins, SKE_TP_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     return SKE_OK;
 }

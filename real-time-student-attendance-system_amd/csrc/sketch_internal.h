@@ -3,6 +3,7 @@
 #include <cstddef>
 
 #include "sketch_common.h"
+#include "sketch_rows_group.h"
 
 namespace ske {
 
@@ -477,6 +478,44 @@ hipError_t launch_rows_last(const RowsLog &L, const uint32_t *pos, uint32_t m, c
 hipError_t launch_rows_gather(const RowsLog &L, const uint32_t *pos, uint32_t m, const RowsWork &W,
                               unsigned long long *out_lec, long long *out_epoch, long long *out_id,
                               uint8_t *out_valid, unsigned grid, int cus, hipStream_t st);
+// The group-by over the sorted positions (DESIGN.md "Row log group-by"; the
+// arithmetic is sketch_rows_group.h's).  The device state of one call: the
+// statistics' accumulators, the median ranks' select state and histograms, and
+// the profile's bins.
+struct RowsGrpDev {
+    unsigned long long n, sum, sumsq, min, max;
+    RowsSel sel;
+    uint32_t hist[2 * kHhSelBins];
+    unsigned long long bins[kTpBins];
+};
+struct RowsGrpWork {
+    uint8_t *gflag;    // m bytes: bit 0 counted, bit 1 the last position of its key run
+    uint32_t *cnt_c;   // rows_cnt_bytes(m): the counted flags' tile counts,
+    uint32_t *cnt_e;   //   the group ends',
+    uint32_t *cnt_l;   //   the listed groups' (over the groups)
+    unsigned long long *gkey;  // per group: its key,
+    uint32_t *gend;            //   the counted prefix at its end
+    unsigned long long *lkey;  // per listed group: its key,
+    uint32_t *lcount;          //   its count
+};
+// D zeroed, min all ones
+hipError_t launch_rows_grp_init(RowsGrpDev *D, hipStream_t st);
+// after launch_rows_last (W.flag = survivor): the two flags per sorted position, their scans, then per
+// group its key and counted prefix; G.cnt_e[0] = groups
+hipError_t launch_rows_grp_flags(const RowsLog &L, const uint32_t *pos, uint32_t m, int by, int valid_filter,
+                                 uint32_t sod_from, const RowsWork &W, const RowsGrpWork &G, unsigned grid, int cus,
+                                 hipStream_t st);
+// over the groups: the counts, the statistics into D, the listed groups compacted to lkey / lcount
+hipError_t launch_rows_grp_counts(const RowsGrpWork &G, uint32_t groups, RowsGrpDev *D, unsigned grid, int cus,
+                                  hipStream_t st);
+// the two median ranks over lcount[0 .. n): D->sel.prefix = med_lo, med_hi
+hipError_t launch_rows_grp_median(const RowsGrpWork &G, uint32_t n, RowsGrpDev *D, unsigned grid, int cus,
+                                  hipStream_t st);
+hipError_t launch_rows_grp_out(const RowsGrpWork &G, uint32_t n, unsigned long long *out_key,
+                               unsigned long long *out_count, unsigned grid, int cus, hipStream_t st);
+// D->bins[tp_bin] += the counted survivors (after launch_rows_last)
+hipError_t launch_rows_profile(const RowsLog &L, const uint32_t *pos, uint32_t m, int valid_filter, uint32_t sod_from,
+                               const RowsWork &W, RowsGrpDev *D, unsigned grid, int cus, hipStream_t st);
 // stable radix sort of (key, pos) pairs by key, signed or unsigned 64 bits (sketch_order.hip; the
 // temporary is kScrSortTmp)
 hipError_t rows_sort_pairs(Scratch *s, bool is_signed, const unsigned long long *keys, unsigned long long *keys_s,
@@ -522,9 +561,11 @@ constexpr int kScratchSlots = 64;
 enum ScratchSlot : int {
     // -- sync
     kScrKeysOrFirst,   // pfadd_exact: sort keys | ske_bf_madd: a link's first-setter table
-                       // (up to 4 x bits bytes) | ske_rows_select: a pass's sort keys; synchronous
-                       // calls all, never at once
-    kScrKeysSorted,    // pfadd_exact (sketch_order.hip), ske_rows_select: sorted keys,
+                       // (up to 4 x bits bytes) | ske_rows_select, ske_rows_group, ske_rows_profile: a
+                       // pass's sort keys, then ske_rows_group's key per group; synchronous calls
+                       // all, never at once
+    kScrKeysSorted,    // pfadd_exact (sketch_order.hip), the row log's reads: sorted keys, then
+                       //   ske_rows_group's key per listed group,
     kScrVals,          //   element indices (ske_rows_select: row positions),
     kScrValsSorted,    //   sorted indices,
     kScrRank,          //   ranks,
@@ -555,8 +596,13 @@ enum ScratchSlot : int {
     kScrHllFmtSize,    // ske_hll_dump_sizes, ske_hll_dump (sketch_api_hll.cpp): a string length per key,
     kScrHllFmtOffs,    //   their exclusive scan (nkeys + 1 offsets),
     kScrHllFmtCard,    //   ske_hll_dump with SKE_HLL_DUMP_CARD: a PFCOUNT per key
-    kScrRowsSelFlag,   // ske_rows_select: a flag byte per row (match, then last of its run),
+    kScrRowsSelFlag,   // ske_rows_select, ske_rows_group, ske_rows_profile: a flag byte per row (match, then
+                       //   last of its run),
     kScrRowsSelCnt,    //   the totals and the per-tile counts of the flags
+    kScrRowsGrpFlag,   // ske_rows_group: the counted and group-end bits per sorted position,
+    kScrRowsGrpCnt,    //   the three tile-count arrays (counted, group ends, listed groups),
+    kScrRowsGrpEnds,   //   the counted prefix at each group's end,
+    kScrRowsGrpCounts, //   the listed groups' counts (u32), which the median select reads
     // -- xr
     kScrXr,            // launch_k1: the XCD-partitioned K1's state (sketch_xr.hip)
     kScrPartRec,       // part_scratch (sketch_part.hip): probe records,
@@ -623,12 +669,14 @@ enum StageSlot : int {
     kStgSeenKeys,      // ske_seen_add / ske_seen_test: the keys,
     kStgSeenMask,      //   ske_seen_add: a mask byte per item,
     kStgSeenOut,       //   the answers on their way to the host
-    kStgRowsLec,       // ske_rows_append: the lecture bytes | ske_rows_select / ske_rows_read: the digests on their way out,
+    kStgRowsLec,       // ske_rows_append: the lecture bytes | ske_rows_select / ske_rows_read: the digests on their way out
+                       //   | ske_rows_group: the keys on their way to the host,
     kStgRowsLecOffs,   //   ske_rows_append: the lecture offsets,
     kStgRowsId,        //   the id bytes | ske_rows_select: the ids on their way to the host,
     kStgRowsIdOffs,    //   the id offsets,
-    kStgRowsEpoch,     //   the epochs (both directions),
+    kStgRowsEpoch,     //   the epochs (both directions) | ske_rows_group: the counts on their way to the host,
     kStgRowsValid,     //   the valid bytes (both directions)
+    kStgRowsGrp,       // ske_rows_group / ske_rows_profile: the statistics, the select state and the bins (RowsGrpDev)
     kStageSlotCount
 };
 

@@ -24,7 +24,8 @@
 // A select reuses the same flag / count / scan machinery twice: over the log's
 // rows (which match), and over the matching positions in sorted order (which
 // is the last of its run of equal keys).  The sort between the two is
-// rows_sort_pairs (sketch_order.hip), one stable pass per key column.
+// rows_sort_pairs (sketch_order.hip), one stable pass per key column.  The
+// group-by and the profile (below, "group-by") start from that same front end.
 #include "sketch_common.h"
 #include "sketch_internal.h"
 
@@ -275,6 +276,204 @@ __global__ void __launch_bounds__(kRowsBlock) k_rows_gather(const RowsLog L, con
     }
 }
 
+// ---- group-by (the arithmetic is sketch_rows_group.h's)
+//
+// Over the sorted positions, after k_rows_last flagged each run's survivor.
+// For BY_STUDENT the id is the sort's last (most significant) pass, for
+// BY_LECTURE the digest, so the rows of a key lie in one run, the keys
+// ascending, and nothing is sorted or moved again:
+//   k_rows_gflag   per position two bits -- counted (survivor and passes the
+//                  filters), group end (the last position of its key run) --
+//                  and per tile the count of each
+//   k_rows_scan    twice: the two tile counts to their prefixes
+//   k_rows_gends   per group end: (key, counted prefix at the end) to its group rank
+//   k_rows_gcount  per group: the count is the step from the group before;
+//                  listed = count > 0, its tile counts; n, sum, sumsq, min, max
+//                  (per thread over its tiles, then the wavefront, then the
+//                  workgroup through LDS, then one set of 64-bit integer
+//                  atomics per workgroup: identical from run to run)
+//   k_rows_scan, k_rows_gplace   the listed groups, compacted in key order
+//   k_rows_sel_hist / k_rows_sel_walk   four rounds: the two median ranks
+// No thread waits for another workgroup.
+
+__device__ __forceinline__ unsigned long long rows_key_of(const RowsLog &L, uint32_t p, int by) {
+    return by == kRowsByStudent ? (unsigned long long)L.id[p] : L.lec[p];
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_ginit(RowsGrpDev *D) {
+    uint32_t *w = reinterpret_cast<uint32_t *>(D);
+    for (uint32_t i = threadIdx.x; i < sizeof(RowsGrpDev) / 4; i += kRowsBlock) w[i] = 0;
+    __syncthreads();
+    if (threadIdx.x == 0) D->min = ~0ull;
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_gflag(const RowsLog L, const uint32_t *pos, uint32_t m, int by,
+                                                            int valid_filter, uint32_t sod_from, const uint8_t *surv,
+                                                            const RowsGrpWork G) {
+    __shared__ unsigned int s_ok[kRowsWaves], s_ref[kRowsWaves];
+    const uint64_t tiles = rows_tiles(m);
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t j = t * kRowsBlock + threadIdx.x;
+        bool counted = false, gend = false;
+        if (j < m) {
+            const uint32_t p = pos[j];
+            counted = surv[j] == 1 && rows_counted(L.valid[p], L.epoch[p], valid_filter, sod_from);
+            gend = j + 1 == m || rows_key_of(L, p, by) != rows_key_of(L, pos[j + 1], by);
+            G.gflag[j] = uint8_t((counted ? 1 : 0) | (gend ? 2 : 0));
+        }
+        rows_tile_count(counted, false, G.cnt_c, tiles, t, s_ok, s_ref);
+        rows_tile_count(gend, false, G.cnt_e, tiles, t, s_ok, s_ref);
+    }
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_gends(const RowsLog L, const uint32_t *pos, uint32_t m, int by,
+                                                            const RowsGrpWork G) {
+    __shared__ unsigned int s_ok[kRowsWaves];
+    const uint64_t tiles = rows_tiles(m);
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t j = t * kRowsBlock + threadIdx.x;
+        const uint32_t f = j < m ? G.gflag[j] : 0;
+        const bool counted = f & 1, gend = f & 2;
+        const uint32_t rc = rows_tile_rank(counted, s_ok);
+        const uint32_t re = rows_tile_rank(gend, s_ok);
+        if (!gend) continue;
+        const uint64_t g = uint64_t(G.cnt_e[4 + t]) + re;
+        G.gkey[g] = rows_key_of(L, pos[j], by);
+        G.gend[g] = G.cnt_c[4 + t] + rc + (counted ? 1u : 0u);
+    }
+}
+
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_min64(unsigned long long v) {
+    for (int o = 32; o; o >>= 1) {
+        const unsigned long long w = __shfl_xor(v, o, 64);
+        v = w < v ? w : v;
+    }
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_max64(unsigned long long v) {
+    for (int o = 32; o; o >>= 1) {
+        const unsigned long long w = __shfl_xor(v, o, 64);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_gcount(const RowsGrpWork G, uint32_t groups, RowsGrpDev *D) {
+    __shared__ unsigned int s_ok[kRowsWaves], s_ref[kRowsWaves];
+    __shared__ unsigned long long s_acc[kRowsWaves][5];
+    const uint64_t tiles = rows_tiles(groups);
+    unsigned long long n = 0, sum = 0, sq = 0, mn = ~0ull, mx = 0;
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t g = t * kRowsBlock + threadIdx.x;
+        const uint32_t c = g < groups ? rows_group_count(G.gend, g) : 0;
+        const bool listed = rows_group_listed(c);
+        if (listed) {
+            n += 1;
+            sum += c;
+            sq += (unsigned long long)c * c;
+            mn = c < mn ? c : mn;
+            mx = c > mx ? c : mx;
+        }
+        rows_tile_count(listed, false, G.cnt_l, tiles, t, s_ok, s_ref);
+    }
+    n = wave_sum64(n), sum = wave_sum64(sum), sq = wave_sum64(sq), mn = wave_min64(mn), mx = wave_max64(mx);
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) s_acc[w][0] = n, s_acc[w][1] = sum, s_acc[w][2] = sq, s_acc[w][3] = mn, s_acc[w][4] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < kRowsWaves; k++) {
+            n += s_acc[k][0], sum += s_acc[k][1], sq += s_acc[k][2];
+            mn = s_acc[k][3] < mn ? s_acc[k][3] : mn;
+            mx = s_acc[k][4] > mx ? s_acc[k][4] : mx;
+        }
+        if (n) {
+            atomicAdd(&D->n, n);
+            atomicAdd(&D->sum, sum);
+            atomicAdd(&D->sumsq, sq);
+            atomicMin(&D->min, mn);
+            atomicMax(&D->max, mx);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_gplace(const RowsGrpWork G, uint32_t groups) {
+    __shared__ unsigned int s_ok[kRowsWaves];
+    const uint64_t tiles = rows_tiles(groups);
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t g = t * kRowsBlock + threadIdx.x;
+        const uint32_t c = g < groups ? rows_group_count(G.gend, g) : 0;
+        const bool listed = rows_group_listed(c);
+        const uint32_t rank = rows_tile_rank(listed, s_ok);
+        if (!listed) continue;
+        const uint64_t o = uint64_t(G.cnt_l[4 + t]) + rank;
+        G.lkey[o] = G.gkey[g];
+        G.lcount[o] = c;
+    }
+}
+
+__global__ void k_rows_sel_begin(RowsGrpDev *D) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) rows_sel_begin(&D->sel, D->n);
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_sel_hist(const uint32_t *counts, uint32_t n, RowsGrpDev *D,
+                                                               uint32_t round) {
+    __shared__ unsigned int s_h[2 * kHhSelBins];
+    for (uint32_t i = threadIdx.x; i < 2 * kHhSelBins; i += kRowsBlock) s_h[i] = 0;
+    __syncthreads();
+    const uint32_t shift = hh_sel_shift(round);
+    const uint32_t p0 = D->sel.prefix[0], p1 = D->sel.prefix[1];
+    const uint64_t stride = uint64_t(gridDim.x) * kRowsBlock;
+    for (uint64_t i = uint64_t(blockIdx.x) * kRowsBlock + threadIdx.x; i < n; i += stride) {
+        const uint32_t v = counts[i], d = hh_sel_digit(v, shift);
+        if (hh_sel_matches(v, p0, shift)) atomicAdd(&s_h[d], 1u);
+        if (hh_sel_matches(v, p1, shift)) atomicAdd(&s_h[kHhSelBins + d], 1u);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < 2 * kHhSelBins; i += kRowsBlock)
+        if (s_h[i]) atomicAdd(&D->hist[i], s_h[i]);
+}
+
+// one workgroup: the walk, then the histograms zero for the next round
+__global__ void __launch_bounds__(kRowsBlock) k_rows_sel_walk(RowsGrpDev *D, uint32_t round) {
+    if (blockIdx.x) return;
+    if (threadIdx.x == 0) rows_sel_step(&D->sel, D->hist, round);
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < 2 * kHhSelBins; i += kRowsBlock) D->hist[i] = 0;
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_gout(const RowsGrpWork G, uint32_t n, unsigned long long *out_key,
+                                                           unsigned long long *out_count) {
+    const uint64_t stride = uint64_t(gridDim.x) * kRowsBlock;
+    for (uint64_t i = uint64_t(blockIdx.x) * kRowsBlock + threadIdx.x; i < n; i += stride) {
+        out_key[i] = G.lkey[i];
+        out_count[i] = G.lcount[i];
+    }
+}
+
+// the counted survivors by weekday and hour: a histogram per workgroup in LDS
+// (a workgroup sees fewer than 2^32 rows), flushed with 64-bit adds
+__global__ void __launch_bounds__(kRowsBlock) k_rows_profile(const RowsLog L, const uint32_t *pos, uint32_t m,
+                                                              int valid_filter, uint32_t sod_from, const uint8_t *surv,
+                                                              RowsGrpDev *D) {
+    __shared__ unsigned int s_b[kTpBins];
+    for (uint32_t i = threadIdx.x; i < kTpBins; i += kRowsBlock) s_b[i] = 0;
+    __syncthreads();
+    const uint64_t stride = uint64_t(gridDim.x) * kRowsBlock;
+    for (uint64_t j = uint64_t(blockIdx.x) * kRowsBlock + threadIdx.x; j < m; j += stride) {
+        if (surv[j] != 1) continue;
+        const uint32_t p = pos[j];
+        const long long e = L.epoch[p];
+        if (rows_counted(L.valid[p], e, valid_filter, sod_from)) atomicAdd(&s_b[tp_bin(tp_time(e))], 1u);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kTpBins; i += kRowsBlock)
+        if (s_b[i]) atomicAdd(&D->bins[i], (unsigned long long)s_b[i]);
+}
+
 unsigned rows_grid(uint64_t n, unsigned grid, int cus) {
     const uint64_t want = rows_tiles(n);
     uint64_t most = grid ? grid : uint64_t(cus) * 8;
@@ -351,6 +550,72 @@ hipError_t launch_rows_gather(const RowsLog &L, const uint32_t *pos, uint32_t m,
     if (m == 0) return hipSuccess;
     hipLaunchKernelGGL(k_rows_gather, dim3(rows_grid(m, grid, cus)), dim3(kRowsBlock), 0, st, L, pos, m, W, out_lec,
                        out_epoch, out_id, out_valid);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_grp_init(RowsGrpDev *D, hipStream_t st) {
+    hipLaunchKernelGGL(k_rows_ginit, dim3(1), dim3(kRowsBlock), 0, st, D);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_grp_flags(const RowsLog &L, const uint32_t *pos, uint32_t m, int by, int valid_filter,
+                                 uint32_t sod_from, const RowsWork &W, const RowsGrpWork &G, unsigned grid, int cus,
+                                 hipStream_t st) {
+    if (m == 0) return hipSuccess;
+    const unsigned g = rows_grid(m, grid, cus);
+    hipLaunchKernelGGL(k_rows_gflag, dim3(g), dim3(kRowsBlock), 0, st, L, pos, m, by, valid_filter, sod_from,
+                       (const uint8_t *)W.flag, G);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = rows_scan(G.cnt_c, m, st);
+    if (e != hipSuccess) return e;
+    e = rows_scan(G.cnt_e, m, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rows_gends, dim3(g), dim3(kRowsBlock), 0, st, L, pos, m, by, G);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_grp_counts(const RowsGrpWork &G, uint32_t groups, RowsGrpDev *D, unsigned grid, int cus,
+                                  hipStream_t st) {
+    if (groups == 0) return hipSuccess;
+    const unsigned g = rows_grid(groups, grid, cus);
+    hipLaunchKernelGGL(k_rows_gcount, dim3(g), dim3(kRowsBlock), 0, st, G, groups, D);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = rows_scan(G.cnt_l, groups, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rows_gplace, dim3(g), dim3(kRowsBlock), 0, st, G, groups);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_grp_median(const RowsGrpWork &G, uint32_t n, RowsGrpDev *D, unsigned grid, int cus,
+                                  hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rows_sel_begin, dim3(1), dim3(64), 0, st, D);
+    hipError_t e = hipGetLastError();
+    const unsigned g = rows_grid(n, grid, cus);
+    for (uint32_t round = 0; round < kHhSelRounds && e == hipSuccess; round++) {
+        hipLaunchKernelGGL(k_rows_sel_hist, dim3(g), dim3(kRowsBlock), 0, st, (const uint32_t *)G.lcount, n, D, round);
+        e = hipGetLastError();
+        if (e != hipSuccess) break;
+        hipLaunchKernelGGL(k_rows_sel_walk, dim3(1), dim3(kRowsBlock), 0, st, D, round);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
+hipError_t launch_rows_grp_out(const RowsGrpWork &G, uint32_t n, unsigned long long *out_key,
+                               unsigned long long *out_count, unsigned grid, int cus, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rows_gout, dim3(rows_grid(n, grid, cus)), dim3(kRowsBlock), 0, st, G, n, out_key, out_count);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_profile(const RowsLog &L, const uint32_t *pos, uint32_t m, int valid_filter, uint32_t sod_from,
+                               const RowsWork &W, RowsGrpDev *D, unsigned grid, int cus, hipStream_t st) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rows_profile, dim3(rows_grid(m, grid, cus)), dim3(kRowsBlock), 0, st, L, pos, m, valid_filter,
+                       sod_from, (const uint8_t *)W.flag, D);
     return hipGetLastError();
 }
 

@@ -14,8 +14,8 @@ import gc
 import numpy as np
 
 from ._lib import (CmsInfo, Context, GenParams, HhInfo, HhStats, IngestDense, SKE_HH_ID_BYTES, SKE_HLL_DUMP_CARD,
-                   SKE_MEM_DEVICE, SKE_MEM_HOST, SKE_TALLY_KEY_BYTES, SKE_TP_BINS, RowsInfo, SeenInfo, SKE_EROWSSPACE,
-                   SketchLibError, TallyInfo)
+                   SKE_MEM_DEVICE, SKE_MEM_HOST, SKE_TALLY_KEY_BYTES, SKE_TP_BINS, RowsGroupStats, RowsInfo, SeenInfo,
+                   SKE_EROWSSPACE, SketchLibError, TallyInfo)
 from . import synthetic
 
 PASS_KINDS = 9  # SKE_PASS_KINDS (include/sketch.h)
@@ -294,6 +294,54 @@ def rows_select(ctx: Context, rid: int, lecture: bytes | None, since: int, until
     if cols is None:
         cols = (np.zeros(0, np.uint64), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.uint8))
     return cols, int(n_out.value), bool(complete.value)
+
+
+def rows_group(ctx: Context, rid: int, by: int, lecture: bytes | None, since: int, until: int, valid_filter: int,
+               sod_from: int, want_groups: bool = True):
+    """ske_rows_group to host arrays: ``(keys u64, counts u64, stats, complete)``
+    -- the groups with at least one counted row in ascending key order (the keys
+    as the call writes them: a student id's two's-complement bits, a lecture's
+    digest) and the fields of ske_rows_group_stats_t as Python ints.  The
+    statistics are asked for first (``cap = 0``), then arrays of ``n`` entries
+    are filled by a second call; ``want_groups`` False stops after the first."""
+    n_out, complete, st = C.c_uint64(), C.c_int(), RowsGroupStats()
+    lec = None if lecture is None else C.c_char_p(lecture)
+    llen = 0 if lecture is None else len(lecture)
+    head = (int(rid), int(by), lec, llen, int(since), int(until), int(valid_filter), int(sod_from))
+
+    def call(keys, counts, cap) -> bool:
+        ptrs = [None, None] if cap == 0 else [keys.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)]
+        try:
+            ctx.call("ske_rows_group", *head, *ptrs, cap, C.byref(n_out), C.byref(st), C.byref(complete),
+                     SKE_MEM_HOST)
+        except SketchLibError as e:
+            if e.code != SKE_EROWSSPACE:
+                raise
+            return False
+        return int(n_out.value) <= cap
+
+    keys, counts = np.zeros(0, np.uint64), np.zeros(0, np.uint64)
+    if not call(keys, counts, 0) and want_groups:
+        cap = int(n_out.value)
+        keys, counts = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+        if not call(keys, counts, cap):
+            raise SketchLibError(SKE_EROWSSPACE, "ERR row log selection does not fit the output")
+    n = int(n_out.value)
+    stats = {k: int(getattr(st, k)) for k, _ in RowsGroupStats._fields_}
+    return keys[:n], counts[:n], stats, bool(complete.value)
+
+
+def rows_profile(ctx: Context, rid: int, lecture: bytes | None, since: int, until: int, valid_filter: int,
+                 sod_from: int):
+    """ske_rows_profile: ``(bins, rows, complete)`` -- the counted rows per
+    weekday (Monday first) and UTC hour as [7, 24] uint64, and the rows of the
+    window after the upsert."""
+    out = np.zeros(SKE_TP_BINS, np.uint64)
+    rows, complete = C.c_uint64(), C.c_int()
+    lec = None if lecture is None else C.c_char_p(lecture)
+    ctx.call("ske_rows_profile", int(rid), lec, 0 if lecture is None else len(lecture), int(since), int(until),
+             int(valid_filter), int(sod_from), out.ctypes.data_as(C.c_void_p), C.byref(rows), C.byref(complete))
+    return out.reshape(7, 24), int(rows.value), bool(complete.value)
 
 
 class SweBatch(C.Structure):

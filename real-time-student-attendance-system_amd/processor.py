@@ -124,7 +124,7 @@ class AttendanceProcessor:
         return rows
 
     def insights(self, keys: Sequence[str] | None = None, k: int = 3, rank_by: str | None = None,
-                 **thresholds) -> list:
+                 exact: bool = False, **thresholds) -> list:
         """attendance_analysis.py:65-118 in its order: ``counts.insights(
         **thresholds)`` with "Lecture Attendance Rankings" (:87-97) at its
         place, after the per-day entries and before the per-student lists of
@@ -135,9 +135,15 @@ class AttendanceProcessor:
           - ``keys`` (lecture-day HLL keys) with ``rank_by`` None or
             ``"unique"``: the unique counts by PFCOUNT (``lecture_rankings(keys,
             k)``);
-          - neither: no such entry."""
+          - neither: no such entry.
+        ``exact=True``: ``counts.exact_insights(k)`` instead -- the five
+        group-bys over the row log, exact (``counts`` needs ``records``)."""
         if self.counts is None:
             raise ValueError("insights need a StudentCounts (counts=)")
+        if exact:
+            if not getattr(self.counts, "keeps_records", False):
+                raise ValueError("exact insights need a StudentCounts with records")
+            return self.counts.exact_insights(k)
         if rank_by not in (None, "unique", "events"):
             raise ValueError('rank_by is None, "unique" or "events"')
         lectured = getattr(self.counts, "counts_lectures", False)
