@@ -9,19 +9,10 @@ using namespace ske;
 
 namespace ske {
 
-void free_cms(Cms &T) {
-    if (T.cells) (void)hipFree(T.cells);
-    T = Cms{};
-}
-
-Cms *get_cms(ske_ctx *c, uint32_t cid) {
-    return cid < c->cms.size() && c->cms[cid].cells ? &c->cms[cid] : nullptr;
-}
-
 CmsTable table_of(const Cms &T) {
     CmsTable D{};
-    D.cells = T.cells;
-    D.count = T.count;
+    D.cells = cms_cells(T);
+    D.count = cms_count(T);
     D.div = T.div;
     D.depth = T.depth;
     D.ncells = T.width * T.depth;
@@ -54,56 +45,23 @@ int ske_cms_init(ske_ctx *c, uint32_t cid, uint32_t width, uint32_t depth) {
     if (width == 0) return SKE_ECMSWIDTH;
     if (depth == 0 || depth > SKE_CMS_MAX_DEPTH) return SKE_ECMSDEPTH;
     if (uint64_t(width) * depth >= SKE_CMS_MAX_CELLS) return SKE_ECMSWIDTH;
-    if (get_cms(c, cid)) return SKE_ECMSEXISTS;
-    if (c->cms.size() <= cid) c->cms.resize(SKE_MAX_CMS);
-    if (!c->cms_lds_ready) {  // the LDS form's private table is larger than the default LDS limit
-        HIPCHK(c, cms_setup());
-        c->cms_lds_ready = true;
-    }
-    // the cells, then the count on the next 16-byte boundary
-    const uint64_t cell_bytes = (uint64_t(width) * depth * 4 + 15) & ~uint64_t(15);
-    uint8_t *p = nullptr;
-    hipError_t e = hipMalloc(&p, cell_bytes + 16);
-    if (e != hipSuccess) {
-        c->last_hip = std::string("hipMalloc(cms): ") + hipGetErrorString(e);
-        return SKE_ENOMEM;
-    }
     Cms T;
-    T.cells = reinterpret_cast<uint32_t *>(p);
-    T.count = reinterpret_cast<unsigned long long *>(p + cell_bytes);
+    T.bytes = ((uint64_t(width) * depth * 4 + 15) & ~uint64_t(15)) + 16;  // the cells, then the count
     T.width = width;
     T.depth = depth;
     T.div = make_div32(width);
-    e = hipMemsetAsync(p, 0, cell_bytes + 16, c->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-    if (e != hipSuccess) {
-        free_cms(T);
-        c->last_hip = std::string("hipMemset(cms): ") + hipGetErrorString(e);
-        return SKE_EHIP;
-    }
-    c->cms[cid] = T;
-    return SKE_OK;
+    return obj_alloc(c, kCmsFamily, c->cms, cid, T, [c](const Cms &N) { return obj_zero(N, N.bytes, c->st); });
 }
 
-int ske_cms_free(ske_ctx *c, uint32_t cid) {
-    if (!c) return SKE_EINVAL;
-    Cms *T = get_cms(c, cid);
-    if (!T) return SKE_ECMSNOKEY;
-    if (c->live_graphs > 0 || c->capturing) {
-        c->last_hip = "a Count-Min Sketch table cannot be freed while a recorded graph may point to it";
-        return SKE_EBUSY;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    free_cms(*T);
-    return SKE_OK;
-}
+int ske_cms_free(ske_ctx *c, uint32_t cid) { return obj_release(c, kCmsFamily, c->cms, cid); }
 
 int ske_cms_info(ske_ctx *c, uint32_t cid, ske_cms_info_t *out) {
     if (!c || !out) return SKE_EINVAL;
-    Cms *T = get_cms(c, cid);
-    if (!T) return SKE_ECMSNOKEY;
+    int rc = SKE_OK;
+    Cms *T = obj_for_sync_call(c, kCmsFamily, c->cms, cid, "ske_cms_info", &rc, kCmsFamily.info_refuses);
+    if (!T) return rc;
     unsigned long long cnt = 0;
-    HIPCHK(c, hipMemcpyAsync(&cnt, T->count, 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(&cnt, cms_count(*T), 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     out->width = T->width;
     out->depth = T->depth;
@@ -213,12 +171,12 @@ int ske_cms_merge(ske_ctx *c, uint32_t dst, const uint32_t *srcs, const int64_t 
         Cms *S = get_cms(c, srcs[k]);
         if (!S) return SKE_ECMSNOKEY;
         if (S->width != D->width || S->depth != D->depth) return SKE_ECMSDIMS;
-        M.src[k] = S->cells;
+        M.src[k] = cms_cells(*S);
         M.w[k] = weights ? weights[k] : 1;
     }
     M.nsrc = nsrc;
     M.ncells = D->width * D->depth;
-    M.dst = D->cells;
+    M.dst = cms_cells(*D);
     int rc = SKE_OK;
     // [0] the check pass's overflow word, [2 + 2k] source k's count
     uint32_t *stg = (uint32_t *)stage_buf(c, kStgCmsFlag, 8 + size_t(nsrc) * 8, &rc);
@@ -226,7 +184,7 @@ int ske_cms_merge(ske_ctx *c, uint32_t dst, const uint32_t *srcs, const int64_t 
     M.flag = stg;
     HIPCHK(c, hipMemsetAsync(stg, 0, 4, c->st));
     for (uint32_t k = 0; k < nsrc; k++)
-        HIPCHK(c, hipMemcpyAsync(stg + 2 + 2 * k, get_cms(c, srcs[k])->count, 8, hipMemcpyDeviceToDevice, c->st));
+        HIPCHK(c, hipMemcpyAsync(stg + 2 + 2 * k, cms_count(*get_cms(c, srcs[k])), 8, hipMemcpyDeviceToDevice, c->st));
     HIPCHK(c, launch_cms_merge(M, false, c->cus, c->st));
     uint64_t h[1 + SKE_CMS_MAX_MERGE];
     HIPCHK(c, hipMemcpyAsync(h, stg, 8 + size_t(nsrc) * 8, hipMemcpyDeviceToHost, c->st));
@@ -237,7 +195,7 @@ int ske_cms_merge(ske_ctx *c, uint32_t dst, const uint32_t *srcs, const int64_t 
     if (cnt < 0 || cnt > (__int128)~0ull) return SKE_ECMSOVERFLOW;
     const unsigned long long cnt64 = (unsigned long long)cnt;
     HIPCHK(c, launch_cms_merge(M, true, c->cus, c->st));
-    HIPCHK(c, hipMemcpyAsync(D->count, &cnt64, 8, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(cms_count(*D), &cnt64, 8, hipMemcpyHostToDevice, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     return SKE_OK;
 }
@@ -248,7 +206,7 @@ int ske_cms_export(ske_ctx *c, uint32_t cid, uint32_t *out, uint64_t cap_cells) 
     if (!T) return SKE_ECMSNOKEY;
     const uint64_t ncells = uint64_t(T->width) * T->depth;
     if (cap_cells < ncells) return SKE_EINVAL;
-    HIPCHK(c, hipMemcpyAsync(out, T->cells, ncells * 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(out, cms_cells(*T), ncells * 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     return SKE_OK;
 }
@@ -258,8 +216,8 @@ int ske_cms_import(ske_ctx *c, uint32_t cid, const uint32_t *in, uint64_t ncells
     Cms *T = get_cms(c, cid);
     if (!T) return SKE_ECMSNOKEY;
     if (ncells != uint64_t(T->width) * T->depth) return SKE_ECMSDIMS;
-    HIPCHK(c, hipMemcpyAsync(T->cells, in, ncells * 4, hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, hipMemcpyAsync(T->count, &count, 8, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(cms_cells(*T), in, ncells * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(cms_count(*T), &count, 8, hipMemcpyHostToDevice, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     return SKE_OK;
 }
@@ -268,7 +226,7 @@ int ske_cms_table_dev(ske_ctx *c, uint32_t cid, void **cells_dev, uint64_t *ncel
     if (!c || !cells_dev || !ncells) return SKE_EINVAL;
     Cms *T = get_cms(c, cid);
     if (!T) return SKE_ECMSNOKEY;
-    *cells_dev = T->cells;
+    *cells_dev = cms_cells(*T);
     *ncells = uint64_t(T->width) * T->depth;
     return SKE_OK;
 }

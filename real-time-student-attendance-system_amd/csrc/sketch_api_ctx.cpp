@@ -395,12 +395,12 @@ int ske_close(ske_ctx *c) {
     (void)hipSetDevice(c->device);
     if (c->st) (void)hipStreamSynchronize(c->st);
     for (auto &F : c->filters) free_filter(F);
-    for (auto &T : c->cms) free_cms(T);
-    for (auto &H : c->hh) free_hh(H);
-    for (auto &P : c->tp) free_tp(P);
-    for (auto &Y : c->tally) free_tally(Y);
-    for (auto &S : c->seen) free_seen(S);
-    for (auto &R : c->rows) free_rows(R);
+    for (auto &T : c->cms) obj_free(T);
+    for (auto &H : c->hh) obj_free(H);
+    for (auto &P : c->tp) obj_free(P);
+    for (auto &Y : c->tally) obj_free(Y);
+    for (auto &S : c->seen) obj_free(S);
+    for (auto &R : c->rows) obj_free(R);
     if (c->regs) (void)hipFree(c->regs);
     if (c->tau) (void)hipFree(c->tau);
     if (c->sig) (void)hipFree(c->sig);

@@ -16,16 +16,11 @@ static_assert(kHhMaxProbes == SKE_HH_MAX_PROBES && kHhLoadDen == SKE_HH_LOAD_DEN
 static_assert((1u << SKE_HH_MIN_LOG2) % 256 == 0, "k_hh_list and k_hhs_est cover the slots with whole blocks");
 static_assert(kHhStatRanks == SKE_HH_MAX_RANKS && sizeof(ske_hh_stats_t) == 56, "sketch.h states the select's ranks");
 
-namespace ske {
-
-void free_hh(Hh &H) {
-    if (H.base) (void)hipFree(H.base);
-    H = Hh{};
+// the set of a hid in use, else nullptr (SKE_EHHNOSET: a hid is not range-checked, kHhFamily)
+static Hh *get_hh(ske_ctx *c, uint32_t hid) {
+    int rc = SKE_OK;
+    return obj_get(kHhFamily, c->hh, hid, &rc);
 }
-
-}  // namespace ske
-
-static Hh *get_hh(ske_ctx *c, uint32_t hid) { return hid < c->hh.size() && c->hh[hid].base ? &c->hh[hid] : nullptr; }
 
 static HhSet set_of(const Hh &H) {
     const uint64_t cap = uint64_t(1) << H.log2;
@@ -45,66 +40,30 @@ static bool hh_use_lds(const ske_ctx *c, const Cms &T) { return uint64_t(T.width
 extern "C" {
 
 int ske_hh_init(ske_ctx *c, uint32_t hid, uint32_t capacity_log2) {
-    if (!c || hid >= SKE_MAX_HH) return SKE_EINVAL;
-    if (capacity_log2 < SKE_HH_MIN_LOG2 || capacity_log2 > SKE_HH_MAX_LOG2) return SKE_EHHCAP;
-    if (get_hh(c, hid)) return SKE_EHHEXISTS;
-    if (c->hh.size() <= hid) c->hh.resize(SKE_MAX_HH);
-    if (!c->hh_lds_ready) {  // the LDS form's table copy is larger than the default LDS limit
-        HIPCHK(c, hh_setup());
-        c->hh_lds_ready = true;
-    }
     Hh H;
     H.log2 = capacity_log2;
-    H.bytes = 16 + (size_t(1) << capacity_log2) * 28;
-    hipError_t e = hipMalloc(&H.base, H.bytes);
-    if (e != hipSuccess) {
-        c->last_hip = std::string("hipMalloc(hh): ") + hipGetErrorString(e);
-        return SKE_ENOMEM;
-    }
-    e = hipMemsetAsync(H.base, 0, H.bytes, c->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-    if (e != hipSuccess) {
-        free_hh(H);
-        c->last_hip = std::string("hipMemset(hh): ") + hipGetErrorString(e);
-        return SKE_EHIP;
-    }
-    c->hh[hid] = H;
-    return SKE_OK;
+    return obj_alloc(c, kHhFamily, c->hh, hid, H, [c](const Hh &N) { return obj_zero(N, N.bytes, c->st); });
 }
 
-int ske_hh_free(ske_ctx *c, uint32_t hid) {
-    if (!c) return SKE_EINVAL;
-    Hh *H = get_hh(c, hid);
-    if (!H) return SKE_EHHNOSET;
-    if (c->live_graphs > 0 || c->capturing) {
-        c->last_hip = "a heavy-hitter set cannot be freed while a recorded graph may point to it";
-        return SKE_EBUSY;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    free_hh(*H);
-    return SKE_OK;
-}
+int ske_hh_free(ske_ctx *c, uint32_t hid) { return obj_release(c, kHhFamily, c->hh, hid); }
 
 int ske_hh_reset(ske_ctx *c, uint32_t hid) {
     if (!c) return SKE_EINVAL;
-    Hh *H = get_hh(c, hid);
-    if (!H) return SKE_EHHNOSET;
-    if (c->capturing) {
-        c->last_hip = "ske_hh_reset waits for the stream and cannot be recorded";
-        return SKE_EBUSY;
-    }
-    HIPCHK(c, hipMemsetAsync(H->base, 0, H->bytes, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
+    int rc = SKE_OK;
+    Hh *H = obj_for_sync_call(c, kHhFamily, c->hh, hid, "ske_hh_reset", &rc);
+    if (!H) return rc;
+    HIPCHK(c, obj_zero(*H, H->bytes, c->st));
     return SKE_OK;
 }
 
 int ske_hh_info(ske_ctx *c, uint32_t hid, ske_hh_info_t *out) {
     if (!c || !out) return SKE_EINVAL;
-    Hh *H = get_hh(c, hid);
-    if (!H) return SKE_EHHNOSET;
+    int rc = SKE_OK;
+    Hh *H = obj_for_sync_call(c, kHhFamily, c->hh, hid, "ske_hh_info", &rc, kHhFamily.info_refuses);
+    if (!H) return rc;
     unsigned int head[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(head, H->base, 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
+    rc = obj_read_head(c, *H, head, 8);
+    if (rc) return rc;
     out->capacity = uint64_t(1) << H->log2;
     out->used = head[0];
     out->overflow = head[1];
@@ -257,17 +216,13 @@ int ske_hh_list(ske_ctx *c, uint32_t hid, uint32_t cid, uint32_t threshold, uint
 int ske_hh_export_dev(ske_ctx *c, uint32_t hid, uint8_t *ids_dev, uint32_t *lens_dev, uint64_t cap, uint64_t *n_out,
                       uint32_t *overflow_out) {
     if (!c || !n_out || !overflow_out) return SKE_EINVAL;
-    Hh *H = get_hh(c, hid);
-    if (!H) return SKE_EHHNOSET;
-    if (c->capturing) {
-        c->last_hip = "ske_hh_export_dev waits for the stream and cannot be recorded";
-        return SKE_EBUSY;
-    }
+    int rc = SKE_OK;
+    Hh *H = obj_for_sync_call(c, kHhFamily, c->hh, hid, "ske_hh_export_dev", &rc);
+    if (!H) return rc;
     if (cap && (!ids_dev || !lens_dev || (reinterpret_cast<uintptr_t>(ids_dev) & 7))) return SKE_EINVAL;
     // no more than the capacity can pass
     const uint64_t slots = uint64_t(1) << H->log2;
     const uint32_t dcap = uint32_t(cap < slots ? cap : slots);
-    int rc = SKE_OK;
     unsigned int *cnt = (unsigned int *)stage_buf(c, kStgHhFlag, 16, &rc);
     if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(cnt, 0, 16, c->st));

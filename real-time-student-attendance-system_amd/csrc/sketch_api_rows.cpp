@@ -29,31 +29,7 @@ static_assert(sizeof(RowsHead) <= kRowsHeadBytes, "the head fits its 64 bytes");
 
 }  // namespace
 
-namespace ske {
-
-void free_rows(Rows &R) {
-    if (R.base) (void)hipFree(R.base);
-    R = Rows{};
-}
-
-}  // namespace ske
-
-static Rows *get_rows(ske_ctx *c, uint32_t rid) {
-    return rid < c->rows.size() && c->rows[rid].base ? &c->rows[rid] : nullptr;
-}
-
-// the log of a rid in use for a call that waits for the stream (so it cannot
-// be recorded); rc: why not
-static Rows *rows_for_sync_call(ske_ctx *c, uint32_t rid, const char *what, int *rc) {
-    if (rid >= SKE_MAX_ROWS) return *rc = SKE_EINVAL, nullptr;
-    Rows *R = get_rows(c, rid);
-    if (!R) return *rc = SKE_EROWSNOLOG, nullptr;
-    if (c->capturing) {
-        c->last_hip = std::string(what) + " waits for the stream and cannot be recorded";
-        return *rc = SKE_EBUSY, nullptr;
-    }
-    return R;
-}
+static_assert(kRowsFamily.head_bytes == kRowsHeadBytes, "the allocation");
 
 static RowsLog log_of(const Rows &R) {
     const uint64_t cap = uint64_t(1) << R.log2;
@@ -66,12 +42,6 @@ static RowsLog log_of(const Rows &R) {
     L.valid = p + cap * 24;
     L.capacity = cap;
     return L;
-}
-
-static int rows_head(ske_ctx *c, const Rows &R, RowsHead *h) {
-    HIPCHK(c, hipMemcpyAsync(h, R.base, sizeof(RowsHead), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    return SKE_OK;
 }
 
 // the four kernels on the context stream; the per-item state is context
@@ -92,9 +62,10 @@ static int rows_enqueue(ske_ctx *c, const Rows &R, RowsItems I) {
 }
 
 static int append_args(ske_ctx *c, uint32_t rid, uint64_t n, const int64_t *epoch, Rows **R) {
-    if (!c || rid >= SKE_MAX_ROWS) return SKE_EINVAL;
-    *R = get_rows(c, rid);
-    if (!*R) return SKE_EROWSNOLOG;
+    if (!c) return SKE_EINVAL;
+    int rc = SKE_OK;
+    *R = obj_get(kRowsFamily, c->rows, rid, &rc);
+    if (!*R) return rc;
     if (n >= 0xffffffffull) return SKE_EINVAL;
     if (n && (!epoch || (reinterpret_cast<uintptr_t>(epoch) & 7))) return SKE_EINVAL;
     return SKE_OK;
@@ -117,7 +88,7 @@ struct RowsFront {
 static int rows_front(ske_ctx *c, const Rows &R, const uint8_t *lec_bytes, uint32_t lec_len, int64_t since,
                       int64_t until, bool id_last, int *complete, RowsFront *F) {
     RowsHead h{};
-    int rc = rows_head(c, R, &h);
+    int rc = obj_read_head(c, R, &h, sizeof h);
     if (rc) return rc;
     *complete = h.overflow ? 0 : 1;
     const uint32_t used = uint32_t(h.used);  // <= 2^28
@@ -193,60 +164,30 @@ static bool rows_filter_ok(int valid_filter, uint32_t sod_from) {
 extern "C" {
 
 int ske_rows_init(ske_ctx *c, uint32_t rid, uint32_t capacity_log2) {
-    if (!c || rid >= SKE_MAX_ROWS) return SKE_EINVAL;
-    if (capacity_log2 < SKE_ROWS_MIN_LOG2 || capacity_log2 > SKE_ROWS_MAX_LOG2) return SKE_EROWSCAP;
-    if (get_rows(c, rid)) return SKE_EROWSEXISTS;
-    if (c->rows.size() <= rid) c->rows.resize(SKE_MAX_ROWS);
     Rows R;
     R.log2 = capacity_log2;
-    R.bytes = kRowsHeadBytes + (size_t(1) << capacity_log2) * SKE_ROWS_ROW_BYTES;
-    hipError_t e = hipMalloc(&R.base, R.bytes);
-    if (e != hipSuccess) {
-        c->last_hip = std::string("hipMalloc(rows): ") + hipGetErrorString(e);
-        return SKE_ENOMEM;
-    }
     // an empty log: the head zero (the columns are read below `used` only)
-    e = hipMemsetAsync(R.base, 0, kRowsHeadBytes, c->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-    if (e != hipSuccess) {
-        free_rows(R);
-        c->last_hip = std::string("hipMemset(rows): ") + hipGetErrorString(e);
-        return SKE_EHIP;
-    }
-    c->rows[rid] = R;
-    return SKE_OK;
+    return obj_alloc(c, kRowsFamily, c->rows, rid, R, [c](const Rows &N) { return obj_zero(N, kRowsHeadBytes, c->st); });
 }
 
-int ske_rows_free(ske_ctx *c, uint32_t rid) {
-    if (!c || rid >= SKE_MAX_ROWS) return SKE_EINVAL;
-    Rows *R = get_rows(c, rid);
-    if (!R) return SKE_EROWSNOLOG;
-    if (c->live_graphs > 0 || c->capturing) {
-        c->last_hip = "a row log cannot be freed while a recorded graph may point to it";
-        return SKE_EBUSY;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    free_rows(*R);
-    return SKE_OK;
-}
+int ske_rows_free(ske_ctx *c, uint32_t rid) { return obj_release(c, kRowsFamily, c->rows, rid); }
 
 int ske_rows_reset(ske_ctx *c, uint32_t rid) {
     if (!c) return SKE_EINVAL;
     int rc = SKE_OK;
-    Rows *R = rows_for_sync_call(c, rid, "ske_rows_reset", &rc);
+    Rows *R = obj_for_sync_call(c, kRowsFamily, c->rows, rid, "ske_rows_reset", &rc);
     if (!R) return rc;
-    HIPCHK(c, hipMemsetAsync(R->base, 0, kRowsHeadBytes, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, obj_zero(*R, kRowsHeadBytes, c->st));
     return SKE_OK;
 }
 
 int ske_rows_info(ske_ctx *c, uint32_t rid, ske_rows_info_t *out) {
     if (!c || !out) return SKE_EINVAL;
     int rc = SKE_OK;
-    Rows *R = rows_for_sync_call(c, rid, "ske_rows_info", &rc);
+    Rows *R = obj_for_sync_call(c, kRowsFamily, c->rows, rid, "ske_rows_info", &rc, kRowsFamily.info_refuses);
     if (!R) return rc;
     RowsHead h{};
-    rc = rows_head(c, *R, &h);
+    rc = obj_read_head(c, *R, &h, sizeof h);
     if (rc) return rc;
     out->capacity = uint64_t(1) << R->log2;
     out->used = h.used;
@@ -349,7 +290,7 @@ int ske_rows_append(ske_ctx *c, uint32_t rid, const uint8_t *lec_bytes, const ui
                     const uint8_t *mask, uint64_t n, int mem) {
     if (!c) return SKE_EINVAL;
     int rc = SKE_OK;
-    Rows *R = rows_for_sync_call(c, rid, "ske_rows_append", &rc);
+    Rows *R = obj_for_sync_call(c, kRowsFamily, c->rows, rid, "ske_rows_append", &rc);
     if (!R) return rc;
     if (n >= 0xffffffffull) return SKE_EINVAL;
     if (n == 0) return SKE_OK;
@@ -400,10 +341,10 @@ int ske_rows_read(ske_ctx *c, uint32_t rid, uint64_t first, uint64_t n, uint64_t
                   int64_t *out_id, uint8_t *out_valid) {
     if (!c) return SKE_EINVAL;
     int rc = SKE_OK;
-    Rows *R = rows_for_sync_call(c, rid, "ske_rows_read", &rc);
+    Rows *R = obj_for_sync_call(c, kRowsFamily, c->rows, rid, "ske_rows_read", &rc);
     if (!R) return rc;
     RowsHead h{};
-    rc = rows_head(c, *R, &h);
+    rc = obj_read_head(c, *R, &h, sizeof h);
     if (rc) return rc;
     if (first > h.used || n > h.used - first) return SKE_EINVAL;
     if (n == 0) return SKE_OK;
@@ -422,7 +363,7 @@ int ske_rows_select(ske_ctx *c, uint32_t rid, const uint8_t *lec_bytes, uint32_t
                     uint64_t cap, uint64_t *n_out, int *complete, int mem) {
     if (!c || !n_out || !complete) return SKE_EINVAL;
     int rc = SKE_OK;
-    Rows *R = rows_for_sync_call(c, rid, "ske_rows_select", &rc);
+    Rows *R = obj_for_sync_call(c, kRowsFamily, c->rows, rid, "ske_rows_select", &rc);
     if (!R) return rc;
     if (cap && (!out_lec || !out_epoch || !out_id || !out_valid)) return SKE_EINVAL;
     *n_out = 0;
@@ -471,7 +412,7 @@ int ske_rows_group(ske_ctx *c, uint32_t rid, int by, const uint8_t *lec_bytes, u
     if (!rows_filter_ok(valid_filter, sod_from)) return SKE_EINVAL;
     if (by != SKE_ROWS_BY_STUDENT && by != SKE_ROWS_BY_LECTURE) return SKE_EINVAL;
     int rc = SKE_OK;
-    Rows *R = rows_for_sync_call(c, rid, "ske_rows_group", &rc);
+    Rows *R = obj_for_sync_call(c, kRowsFamily, c->rows, rid, "ske_rows_group", &rc);
     if (!R) return rc;
     if (cap && (!out_key || !out_count)) return SKE_EINVAL;
     RowsFront F{};
@@ -556,7 +497,7 @@ int ske_rows_profile(ske_ctx *c, uint32_t rid, const uint8_t *lec_bytes, uint32_
     memset(out_bins, 0, SKE_TP_BINS * sizeof(uint64_t));
     if (!rows_filter_ok(valid_filter, sod_from)) return SKE_EINVAL;
     int rc = SKE_OK;
-    Rows *R = rows_for_sync_call(c, rid, "ske_rows_profile", &rc);
+    Rows *R = obj_for_sync_call(c, kRowsFamily, c->rows, rid, "ske_rows_profile", &rc);
     if (!R) return rc;
     RowsFront F{};
     rc = rows_front(c, *R, lec_bytes, lec_len, since, until, false, complete, &F);

@@ -25,31 +25,7 @@ static_assert(sizeof(SeenHead) <= kSeenHeadBytes, "the head fits its 64 bytes");
 
 }  // namespace
 
-namespace ske {
-
-void free_seen(Seen &S) {
-    if (S.base) (void)hipFree(S.base);
-    S = Seen{};
-}
-
-}  // namespace ske
-
-static Seen *get_seen(ske_ctx *c, uint32_t sid) {
-    return sid < c->seen.size() && c->seen[sid].base ? &c->seen[sid] : nullptr;
-}
-
-// the set of a sid in use for a call that waits for the stream (so it cannot
-// be recorded); rc: why not
-static Seen *seen_for_sync_call(ske_ctx *c, uint32_t sid, const char *what, int *rc) {
-    if (sid >= SKE_MAX_SEEN) return *rc = SKE_EINVAL, nullptr;
-    Seen *S = get_seen(c, sid);
-    if (!S) return *rc = SKE_ESEENNOSET, nullptr;
-    if (c->capturing) {
-        c->last_hip = std::string(what) + " waits for the stream and cannot be recorded";
-        return *rc = SKE_EBUSY, nullptr;
-    }
-    return S;
-}
+static_assert(kSeenFamily.head_bytes == kSeenHeadBytes && kSeenFamily.slot_bytes == kSeenSlotBytes, "the allocation");
 
 static SeenTab tab_of(const Seen &S) {
     const uint64_t cap = uint64_t(1) << S.log2;
@@ -71,13 +47,6 @@ static hipError_t seen_clear(const Seen &S, hipStream_t st) {
     if (e == hipSuccess) e = hipMemsetAsync(S.base + kSeenHeadBytes + cap * 16, 0xff, cap * 8, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     return e;
-}
-
-static int seen_head(ske_ctx *c, Seen &S, SeenHead *h) {
-    HIPCHK(c, hipMemcpyAsync(h, S.base, sizeof(SeenHead), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    S.calls_host = h->calls;  // recorded graphs' replays included
-    return SKE_OK;
 }
 
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -112,45 +81,17 @@ static int fold_launch(ske_ctx *c, uint64_t *keys, const SeenCol &C, int begin) 
 extern "C" {
 
 int ske_seen_init(ske_ctx *c, uint32_t sid, uint32_t capacity_log2) {
-    if (!c || sid >= SKE_MAX_SEEN) return SKE_EINVAL;
-    if (capacity_log2 < SKE_SEEN_MIN_LOG2 || capacity_log2 > SKE_SEEN_MAX_LOG2) return SKE_ESEENCAP;
-    if (get_seen(c, sid)) return SKE_ESEENEXISTS;
-    if (c->seen.size() <= sid) c->seen.resize(SKE_MAX_SEEN);
     Seen S;
     S.log2 = capacity_log2;
-    S.bytes = kSeenHeadBytes + (size_t(1) << capacity_log2) * kSeenSlotBytes;
-    hipError_t e = hipMalloc(&S.base, S.bytes);
-    if (e != hipSuccess) {
-        c->last_hip = std::string("hipMalloc(seen): ") + hipGetErrorString(e);
-        return SKE_ENOMEM;
-    }
-    e = seen_clear(S, c->st);
-    if (e != hipSuccess) {
-        free_seen(S);
-        c->last_hip = std::string("hipMemset(seen): ") + hipGetErrorString(e);
-        return SKE_EHIP;
-    }
-    c->seen[sid] = S;
-    return SKE_OK;
+    return obj_alloc(c, kSeenFamily, c->seen, sid, S, [c](const Seen &N) { return seen_clear(N, c->st); });
 }
 
-int ske_seen_free(ske_ctx *c, uint32_t sid) {
-    if (!c || sid >= SKE_MAX_SEEN) return SKE_EINVAL;
-    Seen *S = get_seen(c, sid);
-    if (!S) return SKE_ESEENNOSET;
-    if (c->live_graphs > 0 || c->capturing) {
-        c->last_hip = "a seen set cannot be freed while a recorded graph may point to it";
-        return SKE_EBUSY;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    free_seen(*S);
-    return SKE_OK;
-}
+int ske_seen_free(ske_ctx *c, uint32_t sid) { return obj_release(c, kSeenFamily, c->seen, sid); }
 
 int ske_seen_reset(ske_ctx *c, uint32_t sid) {
     if (!c) return SKE_EINVAL;
     int rc = SKE_OK;
-    Seen *S = seen_for_sync_call(c, sid, "ske_seen_reset", &rc);
+    Seen *S = obj_for_sync_call(c, kSeenFamily, c->seen, sid, "ske_seen_reset", &rc);
     if (!S) return rc;
     HIPCHK(c, seen_clear(*S, c->st));
     S->calls_host = 0;
@@ -160,11 +101,12 @@ int ske_seen_reset(ske_ctx *c, uint32_t sid) {
 int ske_seen_info(ske_ctx *c, uint32_t sid, ske_seen_info_t *out) {
     if (!c || !out) return SKE_EINVAL;
     int rc = SKE_OK;
-    Seen *S = seen_for_sync_call(c, sid, "ske_seen_info", &rc);
+    Seen *S = obj_for_sync_call(c, kSeenFamily, c->seen, sid, "ske_seen_info", &rc, kSeenFamily.info_refuses);
     if (!S) return rc;
     SeenHead h{};
-    rc = seen_head(c, *S, &h);
+    rc = obj_read_head(c, *S, &h, sizeof h);
     if (rc) return rc;
+    S->calls_host = h.calls;  // recorded graphs' replays included
     out->capacity = uint64_t(1) << S->log2;
     out->limit = seen_limit(S->log2);
     out->used = h.used;
@@ -233,9 +175,10 @@ int ske_seen_fold_epoch_async(ske_ctx *c, uint64_t *keys, const int64_t *epoch, 
 
 int ske_seen_add_async(ske_ctx *c, uint32_t sid, const uint64_t *keys, uint64_t n, const uint8_t *mask, int want,
                        uint8_t *out) {
-    if (!c || sid >= SKE_MAX_SEEN) return SKE_EINVAL;
-    Seen *S = get_seen(c, sid);
-    if (!S) return SKE_ESEENNOSET;
+    if (!c) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Seen *S = obj_get(kSeenFamily, c->seen, sid, &rc);
+    if (!S) return rc;
     if (n >= 0xffffffffull) return SKE_EINVAL;
     if (n == 0) return SKE_OK;
     if (!keys || !out || !aligned16(keys)) return SKE_EINVAL;
@@ -243,9 +186,10 @@ int ske_seen_add_async(ske_ctx *c, uint32_t sid, const uint64_t *keys, uint64_t 
 }
 
 int ske_seen_test_async(ske_ctx *c, uint32_t sid, const uint64_t *keys, uint64_t n, uint8_t *present_out) {
-    if (!c || sid >= SKE_MAX_SEEN) return SKE_EINVAL;
-    Seen *S = get_seen(c, sid);
-    if (!S) return SKE_ESEENNOSET;
+    if (!c) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Seen *S = obj_get(kSeenFamily, c->seen, sid, &rc);
+    if (!S) return rc;
     if (n >= 0xffffffffull) return SKE_EINVAL;
     if (n == 0) return SKE_OK;
     if (!keys || !present_out || !aligned16(keys)) return SKE_EINVAL;
@@ -257,7 +201,7 @@ int ske_seen_add(ske_ctx *c, uint32_t sid, const uint64_t *keys, uint64_t n, con
                  uint8_t *out, int mem) {
     if (!c) return SKE_EINVAL;
     int rc = SKE_OK;
-    Seen *S = seen_for_sync_call(c, sid, "ske_seen_add", &rc);
+    Seen *S = obj_for_sync_call(c, kSeenFamily, c->seen, sid, "ske_seen_add", &rc);
     if (!S) return rc;
     if (n >= 0xffffffffull) return SKE_EINVAL;
     if (n == 0) return SKE_OK;
@@ -291,7 +235,7 @@ int ske_seen_add(ske_ctx *c, uint32_t sid, const uint64_t *keys, uint64_t n, con
 int ske_seen_test(ske_ctx *c, uint32_t sid, const uint64_t *keys, uint64_t n, uint8_t *present_out, int mem) {
     if (!c) return SKE_EINVAL;
     int rc = SKE_OK;
-    Seen *S = seen_for_sync_call(c, sid, "ske_seen_test", &rc);
+    Seen *S = obj_for_sync_call(c, kSeenFamily, c->seen, sid, "ske_seen_test", &rc);
     if (!S) return rc;
     if (n >= 0xffffffffull) return SKE_EINVAL;
     if (n == 0) return SKE_OK;

@@ -33,31 +33,7 @@ struct TallyHeadHost {
 
 }  // namespace
 
-namespace ske {
-
-void free_tally(Tally &Y) {
-    if (Y.base) (void)hipFree(Y.base);
-    Y = Tally{};
-}
-
-}  // namespace ske
-
-static Tally *get_tally(ske_ctx *c, uint32_t tid) {
-    return tid < c->tally.size() && c->tally[tid].base ? &c->tally[tid] : nullptr;
-}
-
-// the tally of a tid in use for a call that waits for the stream (so it cannot
-// be recorded); rc: why not
-static Tally *tally_for_sync_call(ske_ctx *c, uint32_t tid, const char *what, int *rc) {
-    if (tid >= SKE_MAX_TALLY) return *rc = SKE_EINVAL, nullptr;
-    Tally *Y = get_tally(c, tid);
-    if (!Y) return *rc = SKE_ETALLYNOSET, nullptr;
-    if (c->capturing) {
-        c->last_hip = std::string(what) + " waits for the stream and cannot be recorded";
-        return *rc = SKE_EBUSY, nullptr;
-    }
-    return Y;
-}
+static_assert(kTallyFamily.head_bytes == kTallyHead && kTallyFamily.slot_bytes == kTallySlotBytes, "the allocation");
 
 static TallyTab tab_of(const Tally &Y) {
     const uint64_t cap = uint64_t(1) << Y.log2;
@@ -80,12 +56,6 @@ static TallyTab tab_of(const Tally &Y) {
 
 static int tally_launch(ske_ctx *c, const Tally &Y, const TallyItems &I) {
     HIPCHK(c, launch_tally_add(tab_of(Y), I, c->tally_form, unsigned(c->tally_grid), c->tally_lds_log2, c->cus, c->st));
-    return SKE_OK;
-}
-
-static int tally_head(ske_ctx *c, const Tally &Y, TallyHeadHost *h) {
-    HIPCHK(c, hipMemcpyAsync(h, Y.base, sizeof(TallyHeadHost), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
     return SKE_OK;
 }
 
@@ -122,7 +92,7 @@ static int tally_fetch(ske_ctx *c, const Tally &Y, uint64_t min_events, uint64_t
     unsigned int n = 0;
     TallyHeadHost h{};
     HIPCHK(c, hipMemcpyAsync(&n, cnt, 4, hipMemcpyDeviceToHost, c->st));
-    rc = tally_head(c, Y, &h);
+    rc = obj_read_head(c, Y, &h, sizeof h);
     if (rc) return rc;
     *n_pass = n;
     *complete = h.overflow == 0;
@@ -171,63 +141,29 @@ static void entry_out(const TallyEntry &e, uint64_t at, uint8_t *keys, uint32_t 
 extern "C" {
 
 int ske_tally_init(ske_ctx *c, uint32_t tid, uint32_t capacity_log2) {
-    if (!c || tid >= SKE_MAX_TALLY) return SKE_EINVAL;
-    if (capacity_log2 < SKE_TALLY_MIN_LOG2 || capacity_log2 > SKE_TALLY_MAX_LOG2) return SKE_ETALLYCAP;
-    if (get_tally(c, tid)) return SKE_ETALLYEXISTS;
-    if (c->tally.size() <= tid) c->tally.resize(SKE_MAX_TALLY);
-    if (!c->tally_ready) {  // form 0's LDS table is larger than the default LDS limit
-        HIPCHK(c, tally_setup());
-        c->tally_ready = true;
-    }
     Tally Y;
     Y.log2 = capacity_log2;
-    Y.bytes = kTallyHead + (size_t(1) << capacity_log2) * kTallySlotBytes;
-    hipError_t e = hipMalloc(&Y.base, Y.bytes);
-    if (e != hipSuccess) {
-        c->last_hip = std::string("hipMalloc(tally): ") + hipGetErrorString(e);
-        return SKE_ENOMEM;
-    }
-    e = hipMemsetAsync(Y.base, 0, Y.bytes, c->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-    if (e != hipSuccess) {
-        free_tally(Y);
-        c->last_hip = std::string("hipMemset(tally): ") + hipGetErrorString(e);
-        return SKE_EHIP;
-    }
-    c->tally[tid] = Y;
-    return SKE_OK;
+    return obj_alloc(c, kTallyFamily, c->tally, tid, Y, [c](const Tally &N) { return obj_zero(N, N.bytes, c->st); });
 }
 
-int ske_tally_free(ske_ctx *c, uint32_t tid) {
-    if (!c || tid >= SKE_MAX_TALLY) return SKE_EINVAL;
-    Tally *Y = get_tally(c, tid);
-    if (!Y) return SKE_ETALLYNOSET;
-    if (c->live_graphs > 0 || c->capturing) {
-        c->last_hip = "a tally cannot be freed while a recorded graph may point to it";
-        return SKE_EBUSY;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    free_tally(*Y);
-    return SKE_OK;
-}
+int ske_tally_free(ske_ctx *c, uint32_t tid) { return obj_release(c, kTallyFamily, c->tally, tid); }
 
 int ske_tally_reset(ske_ctx *c, uint32_t tid) {
     if (!c) return SKE_EINVAL;
     int rc = SKE_OK;
-    Tally *Y = tally_for_sync_call(c, tid, "ske_tally_reset", &rc);
+    Tally *Y = obj_for_sync_call(c, kTallyFamily, c->tally, tid, "ske_tally_reset", &rc);
     if (!Y) return rc;
-    HIPCHK(c, hipMemsetAsync(Y->base, 0, Y->bytes, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, obj_zero(*Y, Y->bytes, c->st));
     return SKE_OK;
 }
 
 int ske_tally_info(ske_ctx *c, uint32_t tid, ske_tally_info_t *out) {
     if (!c || !out) return SKE_EINVAL;
     int rc = SKE_OK;
-    Tally *Y = tally_for_sync_call(c, tid, "ske_tally_info", &rc);
+    Tally *Y = obj_for_sync_call(c, kTallyFamily, c->tally, tid, "ske_tally_info", &rc, kTallyFamily.info_refuses);
     if (!Y) return rc;
     TallyHeadHost h{};
-    rc = tally_head(c, *Y, &h);
+    rc = obj_read_head(c, *Y, &h, sizeof h);
     if (rc) return rc;
     out->capacity = uint64_t(1) << Y->log2;
     out->used = h.used;
@@ -240,9 +176,10 @@ int ske_tally_info(ske_ctx *c, uint32_t tid, ske_tally_info_t *out) {
 
 int ske_tally_add_packed_async(ske_ctx *c, uint32_t tid, const uint8_t *bytes, const uint32_t *offs, uint64_t n,
                                const uint8_t *mask) {
-    if (!c || tid >= SKE_MAX_TALLY) return SKE_EINVAL;
-    Tally *Y = get_tally(c, tid);
-    if (!Y) return SKE_ETALLYNOSET;
+    if (!c) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Tally *Y = obj_get(kTallyFamily, c->tally, tid, &rc);
+    if (!Y) return rc;
     if (n >= 0xffffffffull) return SKE_EINVAL;
     if (n == 0) return SKE_OK;
     if (!bytes || !offs) return SKE_EINVAL;
@@ -257,9 +194,10 @@ int ske_tally_add_packed_async(ske_ctx *c, uint32_t tid, const uint8_t *bytes, c
 
 int ske_tally_add_fixed_async(ske_ctx *c, uint32_t tid, const uint8_t *keys, uint32_t width, uint64_t n,
                               const uint8_t *mask) {
-    if (!c || tid >= SKE_MAX_TALLY) return SKE_EINVAL;
-    Tally *Y = get_tally(c, tid);
-    if (!Y) return SKE_ETALLYNOSET;
+    if (!c) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Tally *Y = obj_get(kTallyFamily, c->tally, tid, &rc);
+    if (!Y) return rc;
     if (width == 0 || n >= 0xffffffffull) return SKE_EINVAL;
     if (n == 0) return SKE_OK;
     if (!keys) return SKE_EINVAL;
@@ -274,9 +212,10 @@ int ske_tally_add_fixed_async(ske_ctx *c, uint32_t tid, const uint8_t *keys, uin
 
 int ske_tally_add_spans_async(ske_ctx *c, uint32_t tid, const uint8_t *bytes, const uint32_t *start,
                               const uint32_t *len, uint64_t n, const uint8_t *status, const uint8_t *mask) {
-    if (!c || tid >= SKE_MAX_TALLY) return SKE_EINVAL;
-    Tally *Y = get_tally(c, tid);
-    if (!Y) return SKE_ETALLYNOSET;
+    if (!c) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Tally *Y = obj_get(kTallyFamily, c->tally, tid, &rc);
+    if (!Y) return rc;
     if (n >= 0xffffffffull) return SKE_EINVAL;
     if (n == 0) return SKE_OK;
     if (!bytes || !start || !len) return SKE_EINVAL;
@@ -295,7 +234,7 @@ int ske_tally_add(ske_ctx *c, uint32_t tid, const uint8_t *bytes, const uint32_t
                   const uint8_t *mask, int mem) {
     if (!c) return SKE_EINVAL;
     int rc = SKE_OK;
-    Tally *Y = tally_for_sync_call(c, tid, "ske_tally_add", &rc);
+    Tally *Y = obj_for_sync_call(c, kTallyFamily, c->tally, tid, "ske_tally_add", &rc);
     if (!Y) return rc;
     if (n >= 0xffffffffull) return SKE_EINVAL;
     if (n == 0) return SKE_OK;
@@ -335,7 +274,7 @@ int ske_tally_query(ske_ctx *c, uint32_t tid, const uint8_t *bytes, const uint32
                     uint64_t *events_out, uint64_t *valid_out, int mem) {
     if (!c) return SKE_EINVAL;
     int rc = SKE_OK;
-    Tally *Y = tally_for_sync_call(c, tid, "ske_tally_query", &rc);
+    Tally *Y = obj_for_sync_call(c, kTallyFamily, c->tally, tid, "ske_tally_query", &rc);
     if (!Y) return rc;
     if (n >= 0xffffffffull) return SKE_EINVAL;
     if (n == 0) return SKE_OK;
@@ -368,7 +307,7 @@ int ske_tally_list(ske_ctx *c, uint32_t tid, uint64_t min_events, uint8_t *out_k
                    uint64_t *out_events, uint64_t *out_valid, uint64_t cap, uint64_t *n_out, int *complete) {
     if (!c || !n_out || !complete) return SKE_EINVAL;
     int rc = SKE_OK;
-    Tally *Y = tally_for_sync_call(c, tid, "ske_tally_list", &rc);
+    Tally *Y = obj_for_sync_call(c, kTallyFamily, c->tally, tid, "ske_tally_list", &rc);
     if (!Y) return rc;
     if (cap && (!out_keys || !out_lens || !out_events || !out_valid)) return SKE_EINVAL;
     std::vector<TallyEntry> v;
@@ -388,7 +327,7 @@ int ske_tally_top(ske_ctx *c, uint32_t tid, uint32_t k, int by, uint8_t *head_ke
                   uint64_t *tail_events, uint64_t *tail_valid, uint64_t *n_out, int *complete) {
     if (!c || !n_out || !complete) return SKE_EINVAL;
     int rc = SKE_OK;
-    Tally *Y = tally_for_sync_call(c, tid, "ske_tally_top", &rc);
+    Tally *Y = obj_for_sync_call(c, kTallyFamily, c->tally, tid, "ske_tally_top", &rc);
     if (!Y) return rc;
     if (k == 0 || k > SKE_TALLY_MAX_TOP || (by != 0 && by != 1)) return SKE_EINVAL;
     if (!head_keys || !head_lens || !head_events || !head_valid || !tail_keys || !tail_lens || !tail_events ||
@@ -414,7 +353,7 @@ int ske_tally_import(ske_ctx *c, uint32_t tid, const uint8_t *keys, const uint32
                      const uint64_t *valid, uint64_t n) {
     if (!c) return SKE_EINVAL;
     int rc = SKE_OK;
-    Tally *Y = tally_for_sync_call(c, tid, "ske_tally_import", &rc);
+    Tally *Y = obj_for_sync_call(c, kTallyFamily, c->tally, tid, "ske_tally_import", &rc);
     if (!Y) return rc;
     if (n >= 0xffffffffull) return SKE_EINVAL;
     if (n == 0) return SKE_OK;
@@ -454,7 +393,7 @@ int ske_tally_export_dev(ske_ctx *c, uint32_t tid, uint8_t *keys_dev, uint32_t *
                          uint64_t *valid_dev, uint64_t cap, uint64_t *n_out) {
     if (!c || !n_out) return SKE_EINVAL;
     int rc = SKE_OK;
-    Tally *Y = tally_for_sync_call(c, tid, "ske_tally_export_dev", &rc);
+    Tally *Y = obj_for_sync_call(c, kTallyFamily, c->tally, tid, "ske_tally_export_dev", &rc);
     if (!Y) return rc;
     if (cap && (!keys_dev || !lens_dev || !events_dev || !valid_dev || (reinterpret_cast<uintptr_t>(keys_dev) & 7)))
         return SKE_EINVAL;
@@ -476,9 +415,10 @@ int ske_tally_export_dev(ske_ctx *c, uint32_t tid, uint8_t *keys_dev, uint32_t *
 int ske_tally_merge_dev(ske_ctx *c, uint32_t tid, const uint8_t *keys_dev, const uint32_t *lens_dev,
                         const uint64_t *events_dev, const uint64_t *valid_dev, uint64_t n, uint64_t dropped_events,
                         uint64_t dropped_valid, uint32_t foreign_overflow) {
-    if (!c || tid >= SKE_MAX_TALLY) return SKE_EINVAL;
-    Tally *Y = get_tally(c, tid);
-    if (!Y) return SKE_ETALLYNOSET;
+    if (!c) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Tally *Y = obj_get(kTallyFamily, c->tally, tid, &rc);
+    if (!Y) return rc;
     if (n >= 0xffffffffull) return SKE_EINVAL;
     if (n && (!keys_dev || !lens_dev || !events_dev || !valid_dev || (reinterpret_cast<uintptr_t>(keys_dev) & 7)))
         return SKE_EINVAL;

@@ -189,11 +189,6 @@ __global__ void __launch_bounds__(kCmsBlock) k_cms_sum(uint32_t *dst, unsigned l
     }
 }
 
-unsigned grid_for(uint64_t n, unsigned block, unsigned cap) {
-    const uint64_t want = (n + block - 1) / block;
-    return unsigned(want < cap ? (want ? want : 1) : cap);
-}
-
 }  // namespace
 
 hipError_t cms_setup() {

@@ -54,6 +54,24 @@ __device__ __forceinline__ uint64_t load_le(const uint8_t *p, uint32_t nb) {
     return v;
 }
 
+// The wavefront append: one entry per passing lane behind *counter.  The passing
+// lanes are counted by one ballot, lane 0 adds the count to *counter once, and a
+// passing lane's entry is the sum before that add plus the passing lanes below
+// it.  Returns the entry's index -- the caller drops an index at or beyond its
+// capacity, so *counter counts all that pass -- or kNoAppend in a lane that does
+// not pass.  Every lane of the wavefront must reach the call (workgroups are
+// whole wavefronts of one dimension).
+constexpr uint32_t kNoAppend = 0xffffffffu;
+__device__ __forceinline__ uint32_t wave_append(bool pass, unsigned int *counter) {
+    const unsigned long long votes = __ballot(pass);
+    if (votes == 0) return kNoAppend;
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(counter, uint32_t(__popcll(votes)));
+    base = __shfl(base, 0, 64);
+    return pass ? base + uint32_t(__popcll(votes & ((1ull << lane) - 1))) : kNoAppend;
+}
+
 // An item held as its first two 8-byte blocks (enough for every student id
 // of the configs: 5..8 decimal digits); longer items re-read blocks 2.. .
 struct Item {

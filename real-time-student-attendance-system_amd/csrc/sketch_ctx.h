@@ -15,6 +15,10 @@
 //   sketch_api_seen.cpp    seen-row sets (exact sets of 128-bit row keys): init, the folds, add, test
 //   sketch_api_rows.cpp    row logs (the attendance rows in arrival order): init, append, select, read
 // A helper used by one unit is static there; what crosses units is declared here.
+// The last six keep "a device allocation owned by the context and addressed by
+// an id": one struct (DevObj), one description per family (ObjFamily) and one
+// set of helpers (obj_get, obj_for_sync_call, obj_alloc, obj_release,
+// obj_read_head) carry the lifecycle; the units hold what is their own.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,55 +54,50 @@ struct Filter {
     bool nonscaling = false;
 };
 
-// one Count-Min Sketch table (cells == nullptr: the cid is free)
-struct Cms {
-    uint32_t *cells = nullptr;            // device: depth rows of width counters, then
-    unsigned long long *count = nullptr;  //   the count, in the same allocation
+// One device object addressed by an id: one allocation owned by the context
+// (base == nullptr: the id is free), its size and, where the family has one,
+// its capacity exponent.  The six families below are this struct, kept in one
+// vector per family (ske_ctx) and handled by the obj_* helpers further down.
+struct DevObj {
+    uint8_t *base = nullptr;  // device
+    size_t bytes = 0;
+    uint32_t log2 = 0;
+};
+
+// one Count-Min Sketch table: depth rows of width counters, then the count on
+// the next 16-byte boundary (the allocation's last 16 bytes)
+struct Cms : DevObj {
     uint32_t width = 0, depth = 0;
     Div32 div{};
 };
+inline uint32_t *cms_cells(const Cms &T) { return reinterpret_cast<uint32_t *>(T.base); }
+inline unsigned long long *cms_count(const Cms &T) {
+    return reinterpret_cast<unsigned long long *>(T.base + T.bytes - 16);
+}
 
-// one heavy-hitter set (base == nullptr: the hid is free); one allocation:
-// a 16-byte head (used, overflow), then the claim words, the id words, the lengths
-struct Hh {
-    uint8_t *base = nullptr;
-    size_t bytes = 0;
-    uint32_t log2 = 0;
-};
+// one heavy-hitter set: a 16-byte head (used, overflow), then the claim words,
+// the id words, the lengths
+using Hh = DevObj;
 
-// one time profile (counts == nullptr: the tid is free): kTpBins u64 counters
-struct Tp {
-    unsigned long long *counts = nullptr;  // device
-};
+// one time profile: kTpBins u64 counters
+using Tp = DevObj;
 
-// one tally (base == nullptr: the tid is free); one allocation: a 64-byte head
-// (used, overflow, taken, the dropped totals), then the claim words, the key
-// words, the two counters and the lengths
-struct Tally {
-    uint8_t *base = nullptr;
-    size_t bytes = 0;
-    uint32_t log2 = 0;
-};
+// one tally: a 64-byte head (used, overflow, taken, the dropped totals), then
+// the claim words, the key words, the two counters and the lengths
+using Tally = DevObj;
 
-// one seen-row set (base == nullptr: the sid is free); one allocation: a 64-byte
-// head (SeenHead), then the w0 words, the w1 words and the stamps
-struct Seen {
-    uint8_t *base = nullptr;
-    size_t bytes = 0;
-    uint32_t log2 = 0;
+// one seen-row set: a 64-byte head (SeenHead), then the w0 words, the w1 words
+// and the stamps
+struct Seen : DevObj {
     // the call counter as the host knows it: the device's at the last ske_seen_info
     // plus the adds enqueued since (a graph's replays are not counted here; the
     // kernels stop the counter themselves)
     uint64_t calls_host = 0;
 };
 
-// one row log (base == nullptr: the rid is free); one allocation: a 64-byte
-// head (RowsHead), then the lec, epoch and id words and the valid bytes
-struct Rows {
-    uint8_t *base = nullptr;
-    size_t bytes = 0;
-    uint32_t log2 = 0;
-};
+// one row log: a 64-byte head (RowsHead), then the lec, epoch and id words and
+// the valid bytes
+using Rows = DevObj;
 
 struct Staged {
     const uint8_t *bytes = nullptr;
@@ -307,26 +306,135 @@ void free_filter(Filter &F);
 // the kernel view of F's chain (cached; the empty chain for a missing key)
 const ChainDev &chain_of(Filter *F);
 
+// ---- the device-object table (Count-Min tables, heavy-hitter sets, time
+// profiles, tallies, seen-row sets, row logs): what a family's calls answer and
+// say.  The two flags are behaviour the families differ in, kept as it is.
+struct ObjFamily {
+    uint32_t max_id;             // ids are 0 .. max_id - 1
+    int e_nosuch, e_exists;      // no object under the id; init of an id in use
+    int e_cap;                   // init with capacity_log2 outside [min_log2, max_log2]
+    uint32_t min_log2, max_log2; //   (max_log2 == 0: the family has no capacity exponent and sizes itself)
+    size_t head_bytes, slot_bytes;  // the allocation: a head, then 2^capacity_log2 slots
+    const char *tag;             // "hipMalloc(tag): ..."
+    const char *noun;            // "<noun> cannot be freed while ..."
+    hipError_t (*setup)();       // the kernels' one-time setup, run by the first init that gets that far
+    bool ske_ctx::*ready;        //   (nullptr: none) and the context's flag that it is done
+    bool id_checked;             // an id >= max_id is SKE_EINVAL in every call (false: only in init; elsewhere e_nosuch)
+    bool info_refuses;           // info refuses while a graph is being recorded (false: it fails on its stream wait)
+};
+constexpr ObjFamily kCmsFamily{SKE_MAX_CMS, SKE_ECMSNOKEY, SKE_ECMSEXISTS, 0, 0, 0, 0, 0, "cms", "a Count-Min Sketch table",
+                               cms_setup, &ske_ctx::cms_lds_ready, false, false};
+constexpr ObjFamily kHhFamily{SKE_MAX_HH, SKE_EHHNOSET, SKE_EHHEXISTS, SKE_EHHCAP, SKE_HH_MIN_LOG2, SKE_HH_MAX_LOG2,
+                              16, 28, "hh", "a heavy-hitter set", hh_setup, &ske_ctx::hh_lds_ready, false, false};
+constexpr ObjFamily kTpFamily{SKE_MAX_TP, SKE_ETPNOSET, SKE_ETPEXISTS, 0, 0, 0, 0, 0, "tp", "a time profile",
+                              nullptr, nullptr, true, true};
+constexpr ObjFamily kTallyFamily{SKE_MAX_TALLY, SKE_ETALLYNOSET, SKE_ETALLYEXISTS, SKE_ETALLYCAP, SKE_TALLY_MIN_LOG2,
+                                 SKE_TALLY_MAX_LOG2, 64, 60, "tally", "a tally", tally_setup, &ske_ctx::tally_ready,
+                                 true, true};
+constexpr ObjFamily kSeenFamily{SKE_MAX_SEEN, SKE_ESEENNOSET, SKE_ESEENEXISTS, SKE_ESEENCAP, SKE_SEEN_MIN_LOG2,
+                                SKE_SEEN_MAX_LOG2, 64, 24, "seen", "a seen set", nullptr, nullptr, true, true};
+constexpr ObjFamily kRowsFamily{SKE_MAX_ROWS, SKE_EROWSNOLOG, SKE_EROWSEXISTS, SKE_EROWSCAP, SKE_ROWS_MIN_LOG2,
+                                SKE_ROWS_MAX_LOG2, 64, SKE_ROWS_ROW_BYTES, "rows", "a row log", nullptr, nullptr, true, true};
+
+// the object of an id in use, else nullptr and *rc: why not
+template <class T>
+T *obj_get(const ObjFamily &F, std::vector<T> &v, uint32_t id, int *rc) {
+    if (F.id_checked && id >= F.max_id) return *rc = SKE_EINVAL, nullptr;
+    if (id < v.size() && v[id].base) return &v[id];
+    return *rc = F.e_nosuch, nullptr;
+}
+
+// the same for a call that waits for the stream, so it cannot be recorded
+// (refuse == false: an info that takes no notice of a recording)
+template <class T>
+T *obj_for_sync_call(ske_ctx *c, const ObjFamily &F, std::vector<T> &v, uint32_t id, const char *what, int *rc,
+                     bool refuse = true) {
+    T *o = obj_get(F, v, id, rc);
+    if (o && refuse && c->capturing) {
+        c->last_hip = std::string(what) + " waits for the stream and cannot be recorded";
+        return *rc = SKE_EBUSY, nullptr;
+    }
+    return o;
+}
+
+template <class T>
+void obj_free(T &o) {
+    if (o.base) (void)hipFree(o.base);
+    o = T{};
+}
+
+// A new object under a free id: o carries log2 (or, in a family without one,
+// bytes) and the family's own fields; clear(o) -- a hipError_t -- makes the
+// allocation an empty object and waits for that.  Stored only when all of it
+// succeeded.
+template <class T, class Clear>
+int obj_alloc(ske_ctx *c, const ObjFamily &F, std::vector<T> &v, uint32_t id, T o, Clear clear) {
+    if (!c || id >= F.max_id) return SKE_EINVAL;
+    if (F.max_log2) {
+        if (o.log2 < F.min_log2 || o.log2 > F.max_log2) return F.e_cap;
+        o.bytes = F.head_bytes + (size_t(1) << o.log2) * F.slot_bytes;
+    }
+    if (id < v.size() && v[id].base) return F.e_exists;
+    if (v.size() <= id) v.resize(F.max_id);
+    if (F.setup && !(c->*F.ready)) {  // an LDS form larger than the default LDS limit
+        const hipError_t e = F.setup();
+        if (e != hipSuccess) {
+            c->last_hip = std::string(F.tag) + "_setup(): " + hipGetErrorString(e);
+            return SKE_EHIP;
+        }
+        c->*F.ready = true;
+    }
+    hipError_t e = hipMalloc(&o.base, o.bytes);
+    if (e != hipSuccess) {
+        c->last_hip = std::string("hipMalloc(") + F.tag + "): " + hipGetErrorString(e);
+        return SKE_ENOMEM;
+    }
+    e = clear(o);
+    if (e != hipSuccess) {
+        obj_free(o);
+        c->last_hip = std::string("hipMemset(") + F.tag + "): " + hipGetErrorString(e);
+        return SKE_EHIP;
+    }
+    v[id] = o;
+    return SKE_OK;
+}
+// the usual clear: `bytes` zero bytes from the base, waited for
+inline hipError_t obj_zero(const DevObj &o, size_t bytes, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(o.base, 0, bytes, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e;
+}
+
+// ske_X_free: not while a graph that may point to the object is recorded or alive
+template <class T>
+int obj_release(ske_ctx *c, const ObjFamily &F, std::vector<T> &v, uint32_t id) {
+    if (!c) return SKE_EINVAL;
+    int rc = SKE_OK;
+    T *o = obj_get(F, v, id, &rc);
+    if (!o) return rc;
+    if (c->live_graphs > 0 || c->capturing) {
+        c->last_hip = std::string(F.noun) + " cannot be freed while a recorded graph may point to it";
+        return SKE_EBUSY;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    obj_free(*o);
+    return SKE_OK;
+}
+
+// the first `bytes` of the allocation on the host, waited for
+inline int obj_read_head(ske_ctx *c, const DevObj &o, void *dst, size_t bytes) {
+    HIPCHK(c, hipMemcpyAsync(dst, o.base, bytes, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SKE_OK;
+}
+
 // ---- sketch_api_cms.cpp
-void free_cms(Cms &T);
-// the table of a cid in use, else nullptr; its kernel view
-Cms *get_cms(ske_ctx *c, uint32_t cid);
+// the table of a cid in use, else nullptr (SKE_ECMSNOKEY: the family has no other answer); its kernel view
+inline Cms *get_cms(ske_ctx *c, uint32_t cid) {
+    int rc = SKE_OK;
+    return obj_get(kCmsFamily, c->cms, cid, &rc);
+}
 CmsTable table_of(const Cms &T);
-
-// ---- sketch_api_hh.cpp
-void free_hh(Hh &H);
-
-// ---- sketch_api_tp.cpp
-void free_tp(Tp &P);
-
-// ---- sketch_api_tally.cpp
-void free_tally(Tally &Y);
-
-// ---- sketch_api_seen.cpp
-void free_seen(Seen &S);
-
-// ---- sketch_api_rows.cpp
-void free_rows(Rows &R);
 
 // ---- sketch_api_swipes.cpp
 bool use_lds(const ske_ctx *c, const ChainDev &ch);

@@ -110,7 +110,7 @@ __global__ void __launch_bounds__(kHhBlock) k_hh_track_global(const CmsTable T, 
 }
 
 // The grid covers the slots exactly (the capacity is a multiple of the block),
-// so every lane of every wavefront reaches the ballot.
+// so every lane of every wavefront reaches the append.
 __global__ void __launch_bounds__(kHhBlock) k_hh_list(const CmsTable T, const HhSet S, uint32_t threshold,
                                                        uint32_t cap, uint64_t *out_ids, uint32_t *out_len,
                                                        uint32_t *out_est, unsigned int *out_n) {
@@ -126,15 +126,8 @@ __global__ void __launch_bounds__(kHhBlock) k_hh_list(const CmsTable T, const Hh
         for (uint32_t r = 0; r < T.depth; r++) est = umin32(est, T.cells[cms_cell(T, it, r)]);
         pass = est >= threshold;
     }
-    const unsigned long long votes = __ballot(pass);
-    if (votes == 0) return;
-    const uint32_t lane = threadIdx.x & 63;
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(out_n, uint32_t(__popcll(votes)));
-    base = __shfl(base, 0, 64);
-    if (!pass) return;
-    const uint32_t at = base + uint32_t(__popcll(votes & ((1ull << lane) - 1)));
-    if (at >= cap) return;
+    const uint32_t at = wave_append(pass, out_n);
+    if (at >= cap) return;  // also the lanes that do not pass
     out_ids[2 * uint64_t(at)] = it.w0;
     out_ids[2 * uint64_t(at) + 1] = it.w1;
     out_len[at] = it.len;
@@ -147,15 +140,8 @@ __global__ void __launch_bounds__(kHhBlock) k_hh_export(const HhSet S, uint32_t 
                                                          uint32_t *out_len, unsigned int *out_n) {
     const uint32_t slot = blockIdx.x * kHhBlock + threadIdx.x;
     const bool pass = S.claim[slot] != 0;
-    const unsigned long long votes = __ballot(pass);
-    if (votes == 0) return;
-    const uint32_t lane = threadIdx.x & 63;
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(out_n, uint32_t(__popcll(votes)));
-    base = __shfl(base, 0, 64);
-    if (!pass) return;
-    const uint32_t at = base + uint32_t(__popcll(votes & ((1ull << lane) - 1)));
-    if (at >= cap) return;
+    const uint32_t at = wave_append(pass, out_n);
+    if (at >= cap) return;  // also the lanes that do not pass
     out_ids[2 * uint64_t(at)] = S.ids[2 * uint64_t(slot)];
     out_ids[2 * uint64_t(at) + 1] = S.ids[2 * uint64_t(slot) + 1];
     out_len[at] = S.len[slot];
@@ -198,15 +184,12 @@ hipError_t launch_hh_track(const CmsTable &T, const CmsItems &I, const HhSet &S,
     if (I.n == 0) return hipSuccess;
     if (lds) {
         if (T.ncells > kCmsLdsCells) return hipErrorInvalidValue;
-        const uint64_t want = (uint64_t(I.n) + kHhLdsBlock - 1) / kHhLdsBlock;
-        const unsigned grid = unsigned(want < uint64_t(cus) ? want : uint64_t(cus));
+        const unsigned grid = grid_for(I.n, kHhLdsBlock, unsigned(cus));
         const size_t lds_bytes = (size_t(T.ncells) * 4 + 15) & ~size_t(15);
         hipLaunchKernelGGL(k_hh_track_lds, dim3(grid), dim3(kHhLdsBlock), lds_bytes, st, T, I, S, threshold, toolong);
     } else {
-        const uint64_t want = (uint64_t(I.n) + kHhBlock - 1) / kHhBlock;
-        const uint64_t most = uint64_t(cus) * 8;
-        hipLaunchKernelGGL(k_hh_track_global, dim3(unsigned(want < most ? want : most)), dim3(kHhBlock), 0, st, T, I,
-                           S, threshold, toolong);
+        hipLaunchKernelGGL(k_hh_track_global, dim3(grid_for(I.n, kHhBlock, unsigned(cus) * 8)), dim3(kHhBlock), 0, st,
+                           T, I, S, threshold, toolong);
     }
     return hipGetLastError();
 }
@@ -231,9 +214,7 @@ hipError_t launch_hh_export(const HhSet &S, uint32_t cap, uint64_t *out_ids, uin
 hipError_t launch_hh_merge(const HhSet &S, const uint64_t *ids, const uint32_t *len, uint32_t n,
                            uint32_t foreign_overflow, int cus, hipStream_t st) {
     if (n == 0 && !foreign_overflow) return hipSuccess;
-    const uint64_t want = (uint64_t(n) + kHhBlock - 1) / kHhBlock;
-    const uint64_t most = uint64_t(cus) * 8;
-    const unsigned grid = unsigned(want < most ? (want ? want : 1) : most);
+    const unsigned grid = grid_for(n, kHhBlock, unsigned(cus) * 8);  // n == 0: the one workgroup sets the word
     hipLaunchKernelGGL(k_hh_merge, dim3(grid), dim3(kHhBlock), 0, st, S, ids, len, n, foreign_overflow);
     return hipGetLastError();
 }

@@ -91,6 +91,7 @@ __global__ void __launch_bounds__(kHhsBlock) k_hhs_est(const CmsTable T, const H
             for (uint32_t r = 0; r < T.depth; r++) est = umin32(est, T.cells[cms_cell(T, it, r)]);
             pass = est >= threshold;
         }
+        // not wave_append: the base is the workgroup's running count in LDS, no counter in memory is added to
         const unsigned long long votes = __ballot(pass);
         if (lane == 0) w_n[it_no & 1][wave] = uint32_t(__popcll(votes));
         __syncthreads();

@@ -460,8 +460,7 @@ hipError_t launch_hll_fmt_load(uint8_t *regs, const uint32_t *slots, uint32_t nk
 
 hipError_t launch_hll_fmt_offs_check(const uint32_t *offs, uint32_t n, unsigned int *bad, int cus, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    const unsigned want = (n + 255) / 256, cap = unsigned(cus) * 4;
-    hipLaunchKernelGGL(k_hll_fmt_offs_check, dim3(want < cap ? want : cap), dim3(256), 0, st, offs, n, bad);
+    hipLaunchKernelGGL(k_hll_fmt_offs_check, dim3(grid_for(n, 256, unsigned(cus) * 4)), dim3(256), 0, st, offs, n, bad);
     return hipGetLastError();
 }
 

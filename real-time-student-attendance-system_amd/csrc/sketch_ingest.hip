@@ -424,12 +424,6 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-static inline unsigned grid_for(uint64_t n, unsigned block, unsigned cap) {
-    uint64_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    return unsigned(g < cap ? g : cap);
-}
-
 // the two kernels above and the flags take `grid` workgroups when it is not 0
 // (SKE_INGEST_GRID: a small batch then walks the stride loop)
 hipError_t launch_ingest_times(const uint8_t *msgs, const IngestCols &c, uint64_t n, int64_t *epoch, int cus,

@@ -7,6 +7,22 @@
 
 namespace ske {
 
+// The grid rule of every launcher whose kernel walks n items in workgroups of
+// `block`: the workgroups that cover n, at most `most` (the kernels stride over
+// the rest).  n == 0 gives one workgroup, never none: most launchers return
+// before they launch for nothing, and those that do launch then (the routing
+// kernels, launch_hh_merge carrying only the overflow word) need the one.
+inline unsigned grid_for(uint64_t n, unsigned block, unsigned most) {
+    const uint64_t cover = (n + block - 1) / block;
+    return unsigned(cover < most ? (cover ? cover : 1) : most);
+}
+// the same where the context carries an override of the most (`grid`; 0: `dflt`
+// stands), itself held to `max`
+inline unsigned grid_for(uint64_t n, unsigned block, unsigned grid, unsigned dflt, unsigned max) {
+    const unsigned most = grid ? grid : dflt;
+    return grid_for(n, block, most < max ? most : max);
+}
+
 // sketch_kernels.hip
 hipError_t launch_swipes(int mode, const ChainDev &ch, bool lds, int tile, const uint8_t *bytes,
                          const uint32_t *offs, uint32_t fixed_w, const uint32_t *slot, uint64_t n,

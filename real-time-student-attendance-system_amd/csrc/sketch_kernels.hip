@@ -666,12 +666,6 @@ __global__ void __launch_bounds__(256)
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-static inline unsigned grid_for(uint64_t n, unsigned block, unsigned cap) {
-    uint64_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    return unsigned(g < cap ? g : cap);
-}
-
 template <int kMode, int U>
 static hipError_t launch_swipes_u(const ChainDev &ch, bool lds, const uint8_t *bytes,
                                   const uint32_t *offs, uint32_t fixed_w, const uint32_t *slot, uint64_t n,

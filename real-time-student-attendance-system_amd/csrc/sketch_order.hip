@@ -86,12 +86,6 @@ void scratch_delete(Scratch *s) {
     delete s;
 }
 
-static inline unsigned grid_for(uint64_t n, unsigned block, unsigned cap) {
-    uint64_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    return unsigned(g < cap ? g : cap);
-}
-
 #define SKE_GRID_LOOP(i, n)                                                                       \
     for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < (n);                   \
          i += uint64_t(gridDim.x) * blockDim.x)

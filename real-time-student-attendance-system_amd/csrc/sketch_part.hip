@@ -1109,12 +1109,6 @@ __global__ void __launch_bounds__(BT) k_part_c_fl(const PartArgs A) {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-static inline unsigned part_grid(uint64_t n, unsigned block, unsigned cap) {
-    uint64_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    return unsigned(g < cap ? g : cap);
-}
-
 // probes per swipe an instantiation of pass A holds: 11 (C3/C5's k = 11
 // filter; two blocks per CU) or 22; 0: the chain is not supported
 static uint32_t part_km(uint32_t ksum) {
@@ -1313,11 +1307,11 @@ hipError_t launch_swipes_part(const ChainDev &ch, const PartBatch *bt, uint32_t 
             if (hook) hook(hook_user, 2, 0, st);
             if (flist) {
                 const unsigned gc =
-                    (part_grid(ms, kPTile * kPbGroup, unsigned(cus) * kPcFlBlocksPerCu) + kPGroups - 1) /
+                    (grid_for(ms, kPTile * kPbGroup, unsigned(cus) * kPcFlBlocksPerCu) + kPGroups - 1) /
                     kPGroups * kPGroups;
                 hipLaunchKernelGGL((k_part_c_fl<kPcFlT, kPTile / kPcFlT>), dim3(gc), dim3(kPcFlT), 0, st, A);
             } else {
-                const unsigned gc = (part_grid(ms, kPcBlock * 2, unsigned(cus) * 8) + kPGroups - 1) / kPGroups * kPGroups;
+                const unsigned gc = (grid_for(ms, kPcBlock * 2, unsigned(cus) * 8) + kPGroups - 1) / kPGroups * kPGroups;
                 hipLaunchKernelGGL(k_part_c<2>, dim3(gc), dim3(kPcBlock), 0, st, A);
             }
             if (hook) hook(hook_user, 2, 1, st);

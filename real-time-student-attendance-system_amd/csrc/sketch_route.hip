@@ -317,8 +317,7 @@ hipError_t launch_route_cap(const uint8_t *ids, uint32_t width, const uint32_t *
         hipLaunchKernelGGL(k_route_scan, dim3(1), dim3(1024), 0, st, R);
         hipLaunchKernelGGL(k_route_scatter_cap, dim3(R.nblocks), dim3(kRtBlock), 0, st, R, cap);
     }
-    const uint64_t g = (uint64_t(cap) + 255) / 256;
-    const unsigned gx = unsigned(g < uint64_t(cus) * 4 / world + 1 ? g : uint64_t(cus) * 4 / world + 1);
+    const unsigned gx = grid_for(cap, 256, unsigned(cus) * 4 / world + 1);
     hipLaunchKernelGGL(k_route_pad, dim3(gx, world), dim3(256), 0, st, R, cap, sink);
     return hipGetLastError();
 }
@@ -361,8 +360,7 @@ hipError_t launch_route_slots(const uint32_t *gkey, uint64_t n, const uint32_t *
     if (n == 0) return hipSuccess;
     // four keys per thread when both arrays are 16-B aligned, else one
     const bool v4 = !(reinterpret_cast<uintptr_t>(gkey) & 15) && !(reinterpret_cast<uintptr_t>(out) & 15);
-    const uint64_t g = ((v4 ? n / 4 : n) + 255) / 256;
-    const unsigned grid = unsigned(g < 1 ? 1 : g < uint64_t(cus) * 8 ? g : uint64_t(cus) * 8);
+    const unsigned grid = grid_for(v4 ? n / 4 : n, 256, unsigned(cus) * 8);  // n < 4: the one workgroup
     if (v4)
         hipLaunchKernelGGL(k_route_slots, dim3(grid), dim3(256), 0, st, gkey, n, kroute, nkeys, world, out);
     else
@@ -423,8 +421,7 @@ __global__ void __launch_bounds__(256) k_pack_bits(const uint8_t *in, uint64_t n
 
 hipError_t launch_pack_bits(const uint8_t *in, uint64_t n, uint8_t *out, int cus, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    const uint64_t g = ((n + 7) / 8 + 255) / 256;
-    const unsigned grid = unsigned(g < uint64_t(cus) * 8 ? g : uint64_t(cus) * 8);
+    const unsigned grid = grid_for((n + 7) / 8, 256, unsigned(cus) * 8);
     hipLaunchKernelGGL(k_pack_bits, dim3(grid), dim3(256), 0, st, in, n, out);
     return hipGetLastError();
 }
@@ -435,8 +432,7 @@ hipError_t launch_route_return(const uint8_t *ans, const uint32_t *pos, uint64_t
                                hipStream_t st) {
     if (n == 0) return hipSuccess;
     const bool v4 = (reinterpret_cast<uintptr_t>(pos) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
-    const uint64_t g = ((v4 ? n / 4 : n) + 255) / 256;
-    const unsigned grid = unsigned(g < 1 ? 1 : g < uint64_t(cus) * 8 ? g : uint64_t(cus) * 8);
+    const unsigned grid = grid_for(v4 ? n / 4 : n, 256, unsigned(cus) * 8);  // n < 4: the one workgroup
     if (v4)
         hipLaunchKernelGGL(k_route_return4, dim3(grid), dim3(256), 0, st, ans, pos, n, out);
     else

@@ -474,11 +474,9 @@ __global__ void __launch_bounds__(kRowsBlock) k_rows_profile(const RowsLog L, co
         if (s_b[i]) atomicAdd(&D->bins[i], (unsigned long long)s_b[i]);
 }
 
-unsigned rows_grid(uint64_t n, unsigned grid, int cus) {
-    const uint64_t want = rows_tiles(n);
-    uint64_t most = grid ? grid : uint64_t(cus) * 8;
-    if (most > kRowsMaxGrid) most = kRowsMaxGrid;
-    return unsigned(want < most ? want : most);
+// workgroups of a kernel over n items: the context's override, else eight per CU
+unsigned grid_of(uint64_t n, unsigned grid, int cus) {
+    return grid_for(n, kRowsBlock, grid, unsigned(cus) * 8, kRowsMaxGrid);
 }
 
 hipError_t rows_scan(uint32_t *cnt, uint64_t n, hipStream_t st) {
@@ -505,7 +503,7 @@ hipError_t rows_append_kind(const RowsLog &L, const RowsItems &I, const RowsWork
 hipError_t launch_rows_append(const RowsLog &L, const RowsItems &I, const RowsWork &W, unsigned grid, int cus,
                               hipStream_t st) {
     if (I.n == 0) return hipSuccess;
-    const unsigned g = rows_grid(I.n, grid, cus);
+    const unsigned g = grid_of(I.n, grid, cus);
     switch (I.kind) {
     case 0: return rows_append_kind<0>(L, I, W, g, st);
     case 1: return rows_append_kind<1>(L, I, W, g, st);
@@ -518,7 +516,7 @@ hipError_t launch_rows_match(const RowsLog &L, uint32_t m, bool by_lec, unsigned
                              long long until, const RowsWork &W, uint32_t *pos_out, unsigned grid, int cus,
                              hipStream_t st) {
     if (m == 0) return hipSuccess;
-    const unsigned g = rows_grid(m, grid, cus);
+    const unsigned g = grid_of(m, grid, cus);
     hipLaunchKernelGGL(k_rows_match, dim3(g), dim3(kRowsBlock), 0, st, L, m, by_lec ? 1 : 0, digest, since, until, W);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -531,14 +529,14 @@ hipError_t launch_rows_match(const RowsLog &L, uint32_t m, bool by_lec, unsigned
 hipError_t launch_rows_keys(const RowsLog &L, const uint32_t *pos, uint32_t m, int col, unsigned long long *key_out,
                             unsigned grid, int cus, hipStream_t st) {
     if (m == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rows_keys, dim3(rows_grid(m, grid, cus)), dim3(kRowsBlock), 0, st, L, pos, m, col, key_out);
+    hipLaunchKernelGGL(k_rows_keys, dim3(grid_of(m, grid, cus)), dim3(kRowsBlock), 0, st, L, pos, m, col, key_out);
     return hipGetLastError();
 }
 
 hipError_t launch_rows_last(const RowsLog &L, const uint32_t *pos, uint32_t m, const RowsWork &W, unsigned grid,
                             int cus, hipStream_t st) {
     if (m == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rows_last, dim3(rows_grid(m, grid, cus)), dim3(kRowsBlock), 0, st, L, pos, m, W);
+    hipLaunchKernelGGL(k_rows_last, dim3(grid_of(m, grid, cus)), dim3(kRowsBlock), 0, st, L, pos, m, W);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return rows_scan(W.cnt, m, st);
@@ -548,7 +546,7 @@ hipError_t launch_rows_gather(const RowsLog &L, const uint32_t *pos, uint32_t m,
                               unsigned long long *out_lec, long long *out_epoch, long long *out_id,
                               uint8_t *out_valid, unsigned grid, int cus, hipStream_t st) {
     if (m == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rows_gather, dim3(rows_grid(m, grid, cus)), dim3(kRowsBlock), 0, st, L, pos, m, W, out_lec,
+    hipLaunchKernelGGL(k_rows_gather, dim3(grid_of(m, grid, cus)), dim3(kRowsBlock), 0, st, L, pos, m, W, out_lec,
                        out_epoch, out_id, out_valid);
     return hipGetLastError();
 }
@@ -562,7 +560,7 @@ hipError_t launch_rows_grp_flags(const RowsLog &L, const uint32_t *pos, uint32_t
                                  uint32_t sod_from, const RowsWork &W, const RowsGrpWork &G, unsigned grid, int cus,
                                  hipStream_t st) {
     if (m == 0) return hipSuccess;
-    const unsigned g = rows_grid(m, grid, cus);
+    const unsigned g = grid_of(m, grid, cus);
     hipLaunchKernelGGL(k_rows_gflag, dim3(g), dim3(kRowsBlock), 0, st, L, pos, m, by, valid_filter, sod_from,
                        (const uint8_t *)W.flag, G);
     hipError_t e = hipGetLastError();
@@ -578,7 +576,7 @@ hipError_t launch_rows_grp_flags(const RowsLog &L, const uint32_t *pos, uint32_t
 hipError_t launch_rows_grp_counts(const RowsGrpWork &G, uint32_t groups, RowsGrpDev *D, unsigned grid, int cus,
                                   hipStream_t st) {
     if (groups == 0) return hipSuccess;
-    const unsigned g = rows_grid(groups, grid, cus);
+    const unsigned g = grid_of(groups, grid, cus);
     hipLaunchKernelGGL(k_rows_gcount, dim3(g), dim3(kRowsBlock), 0, st, G, groups, D);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -593,7 +591,7 @@ hipError_t launch_rows_grp_median(const RowsGrpWork &G, uint32_t n, RowsGrpDev *
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_rows_sel_begin, dim3(1), dim3(64), 0, st, D);
     hipError_t e = hipGetLastError();
-    const unsigned g = rows_grid(n, grid, cus);
+    const unsigned g = grid_of(n, grid, cus);
     for (uint32_t round = 0; round < kHhSelRounds && e == hipSuccess; round++) {
         hipLaunchKernelGGL(k_rows_sel_hist, dim3(g), dim3(kRowsBlock), 0, st, (const uint32_t *)G.lcount, n, D, round);
         e = hipGetLastError();
@@ -607,14 +605,14 @@ hipError_t launch_rows_grp_median(const RowsGrpWork &G, uint32_t n, RowsGrpDev *
 hipError_t launch_rows_grp_out(const RowsGrpWork &G, uint32_t n, unsigned long long *out_key,
                                unsigned long long *out_count, unsigned grid, int cus, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rows_gout, dim3(rows_grid(n, grid, cus)), dim3(kRowsBlock), 0, st, G, n, out_key, out_count);
+    hipLaunchKernelGGL(k_rows_gout, dim3(grid_of(n, grid, cus)), dim3(kRowsBlock), 0, st, G, n, out_key, out_count);
     return hipGetLastError();
 }
 
 hipError_t launch_rows_profile(const RowsLog &L, const uint32_t *pos, uint32_t m, int valid_filter, uint32_t sod_from,
                                const RowsWork &W, RowsGrpDev *D, unsigned grid, int cus, hipStream_t st) {
     if (m == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rows_profile, dim3(rows_grid(m, grid, cus)), dim3(kRowsBlock), 0, st, L, pos, m, valid_filter,
+    hipLaunchKernelGGL(k_rows_profile, dim3(grid_of(m, grid, cus)), dim3(kRowsBlock), 0, st, L, pos, m, valid_filter,
                        sod_from, (const uint8_t *)W.flag, D);
     return hipGetLastError();
 }

@@ -258,16 +258,14 @@ __global__ void __launch_bounds__(kSeenBlock) k_seen_test(const SeenTab T, const
     }
 }
 
-unsigned seen_grid(uint32_t n, unsigned grid, int cus) {
-    const uint64_t want = (uint64_t(n) + kSeenBlock - 1) / kSeenBlock;
-    uint64_t most = grid ? grid : uint64_t(cus) * 8;
-    if (most > kSeenMaxGrid) most = kSeenMaxGrid;
-    return unsigned(want < most ? want : most);
+// workgroups of a kernel over n items: the context's override, else eight per CU
+unsigned grid_of(uint32_t n, unsigned grid, int cus) {
+    return grid_for(n, kSeenBlock, grid, unsigned(cus) * 8, kSeenMaxGrid);
 }
 
 template <int kKind>
 hipError_t seen_fold_kind(uint64_t *keys, const SeenCol &C, bool begin, unsigned grid, int cus, hipStream_t st) {
-    hipLaunchKernelGGL(k_seen_fold<kKind>, dim3(seen_grid(C.n, grid, cus)), dim3(kSeenBlock), 0, st, keys, C,
+    hipLaunchKernelGGL(k_seen_fold<kKind>, dim3(grid_of(C.n, grid, cus)), dim3(kSeenBlock), 0, st, keys, C,
                        begin ? 1 : 0);
     return hipGetLastError();
 }
@@ -288,7 +286,7 @@ hipError_t launch_seen_fold(uint64_t *keys, const SeenCol &C, bool begin, unsign
 hipError_t launch_seen_add(const SeenTab &T, const uint64_t *keys, uint32_t n, const uint8_t *mask, uint32_t want,
                            uint32_t *slot, uint8_t *out, unsigned grid, int cus, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    const unsigned g = seen_grid(n, grid, cus);
+    const unsigned g = grid_of(n, grid, cus);
     hipLaunchKernelGGL(k_seen_walk, dim3(g), dim3(kSeenBlock), 0, st, T, keys, n, mask, want, slot);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -302,7 +300,7 @@ hipError_t launch_seen_add(const SeenTab &T, const uint64_t *keys, uint32_t n, c
 hipError_t launch_seen_test(const SeenTab &T, const uint64_t *keys, uint32_t n, uint8_t *present, unsigned grid,
                             int cus, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_seen_test, dim3(seen_grid(n, grid, cus)), dim3(kSeenBlock), 0, st, T, keys, n, present);
+    hipLaunchKernelGGL(k_seen_test, dim3(grid_of(n, grid, cus)), dim3(kSeenBlock), 0, st, T, keys, n, present);
     return hipGetLastError();
 }
 

@@ -299,7 +299,7 @@ __global__ void __launch_bounds__(kTallyBlock) k_tally_query(const TallyTab T, c
 }
 
 // The grid covers the slots exactly (the capacity is a multiple of the block),
-// so every lane of every wavefront reaches the ballot.
+// so every lane of every wavefront reaches the append.
 __global__ void __launch_bounds__(kTallyBlock) k_tally_list(const TallyTab T, uint64_t min_events, uint32_t cap,
                                                              uint64_t *out_keys, uint32_t *out_len, uint64_t *out_ev,
                                                              uint64_t *out_va, unsigned int *out_n) {
@@ -310,15 +310,8 @@ __global__ void __launch_bounds__(kTallyBlock) k_tally_list(const TallyTab T, ui
         ev = T.events[slot];
         pass = ev >= min_events;
     }
-    const unsigned long long votes = __ballot(pass);
-    if (votes == 0) return;
-    const uint32_t lane = threadIdx.x & 63;
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(out_n, uint32_t(__popcll(votes)));
-    base = __shfl(base, 0, 64);
-    if (!pass) return;
-    const uint32_t at = base + uint32_t(__popcll(votes & ((1ull << lane) - 1)));
-    if (at >= cap) return;
+    const uint32_t at = wave_append(pass, out_n);
+    if (at >= cap) return;  // also the lanes that do not pass
 #pragma unroll
     for (uint32_t j = 0; j < kTallyKeyWords; j++)
         out_keys[kTallyKeyWords * uint64_t(at) + j] = T.keys[kTallyKeyWords * uint64_t(slot) + j];
@@ -347,19 +340,14 @@ hipError_t tally_launch_kind(const TallyTab &T, const TallyItems &I, int form, u
                              hipStream_t st) {
     if constexpr (kKind != 3) {  // a listing is imported through form 1 alone
         if (form == 0) {
-            const uint64_t want = (uint64_t(I.n) + kTallyLdsBlock - 1) / kTallyLdsBlock;
-            if (grid == 0) grid = unsigned(cus);
-            if (grid > kTallyMaxGrid) grid = kTallyMaxGrid;
-            if (grid > want) grid = unsigned(want);
+            grid = grid_for(I.n, kTallyLdsBlock, grid, unsigned(cus), kTallyMaxGrid);
             hipLaunchKernelGGL(k_tally_add_lds<kKind>, dim3(grid), dim3(kTallyLdsBlock), tally_lds_bytes(lds_log2),
                                st, T, I, uint32_t(lds_log2));
             return hipGetLastError();
         }
     }
-    const uint64_t want = (uint64_t(I.n) + kTallyBlock - 1) / kTallyBlock;
-    const uint64_t most = uint64_t(cus) * 8;
-    hipLaunchKernelGGL(k_tally_add_global<kKind>, dim3(unsigned(want < most ? want : most)), dim3(kTallyBlock), 0, st,
-                       T, I);
+    hipLaunchKernelGGL(k_tally_add_global<kKind>, dim3(grid_for(I.n, kTallyBlock, unsigned(cus) * 8)),
+                       dim3(kTallyBlock), 0, st, T, I);
     return hipGetLastError();
 }
 
@@ -395,10 +383,8 @@ hipError_t launch_tally_query(const TallyTab &T, const TallyItems &I, uint64_t *
                               hipStream_t st) {
     if (I.n == 0) return hipSuccess;
     if (I.kind != 0) return hipErrorInvalidValue;
-    const uint64_t want = (uint64_t(I.n) + kTallyBlock - 1) / kTallyBlock;
-    const uint64_t most = uint64_t(cus) * 8;
-    hipLaunchKernelGGL(k_tally_query<0>, dim3(unsigned(want < most ? want : most)), dim3(kTallyBlock), 0, st, T, I, ev,
-                       va);
+    hipLaunchKernelGGL(k_tally_query<0>, dim3(grid_for(I.n, kTallyBlock, unsigned(cus) * 8)), dim3(kTallyBlock), 0, st,
+                       T, I, ev, va);
     return hipGetLastError();
 }
 

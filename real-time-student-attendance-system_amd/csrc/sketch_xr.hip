@@ -280,12 +280,6 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-static inline unsigned grid_for(uint64_t n, unsigned block, unsigned cap) {
-    uint64_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    return unsigned(g < cap ? g : cap);
-}
-
 bool xr_supported(const ChainDev &ch) {
     if (ch.nlinks < 1 || ch.nlinks > kXrMaxLinks) return false;
     for (int l = 0; l < ch.nlinks; l++)
