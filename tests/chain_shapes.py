@@ -273,6 +273,7 @@ LDS_MAX = 152 * 1024
 XR_BATCH_K, XR_MAX_LINKS, XR_MAX_K, XR_KB = 16, 8, 31, (7, 8, 10, 11, 13, 16)
 P_MAX_LINKS, P_MAX_SLICES, P_SLICE_LOG, P_KM = 8, 2047, 19, (11, 22)
 XR_MIN_BYTES = 8 << 20
+XR_REGIONS, XR_SLICE_ALIGN = 8, 1024    # sketch_xr.hip: one slice of every link per XCD, a multiple of 1024 bits
 
 
 def csrc_constants() -> dict:
@@ -299,6 +300,19 @@ def csrc_constants() -> dict:
         P_SLICE_LOG=const(inl, "kPSliceLog"),
         P_KM=tuple(int(b) for a, b in re.findall(r"if \(ksum <= (\d+)\) return (\d+);", part) if a == b),
         XR_MIN_BYTES=const(api, "kXrMinBytes"))
+
+
+def csrc_cut_constants() -> dict:
+    """The constants of xr_cuts as csrc/ holds them now: kRegions, and the
+    alignment A of both region kernels' ``slice = ((d + kRegions - 1) / kRegions + A - 1) & ~(A - 1)``."""
+    def src(name):
+        with open(os.path.join(CSRC, name)) as f:
+            return f.read()
+
+    m = re.search(r"constexpr\s+\w+\s+kRegions\s*=\s*(\d+);", src("sketch_common.h"))
+    found = re.findall(r"slice = \(\(d \+ kRegions - 1\) / kRegions \+ (\d+)\) & ~(\d+)u;", src("sketch_xr.hip"))
+    assert m and len(found) == 2 and len(set(found)) == 1 and found[0][0] == found[0][1], (m, found)
+    return dict(XR_REGIONS=int(m.group(1)), XR_SLICE_ALIGN=int(found[0][0]) + 1)
 
 
 def _pad16(bits):
@@ -340,6 +354,14 @@ def xr_kb(specs):
         return None
     kmax = max(k for _, k in specs)
     return next(kb for kb in XR_KB if kmax <= kb) if kmax <= XR_BATCH_K else 0
+
+
+def xr_cuts(bits):
+    """k_xr_region / k_xr_region_b: region r = 1 .. 7 of a link tests the bits
+    from ``r * slice``, slice = ceil(bits / 8) rounded up to 1024 bits; the bit
+    positions where one region ends and the next begins."""
+    per = ((bits + XR_REGIONS - 1) // XR_REGIONS + XR_SLICE_ALIGN - 1) & ~(XR_SLICE_ALIGN - 1)
+    return tuple(r * per for r in range(1, XR_REGIONS) if r * per < bits)
 
 
 def plan(specs, variant):
