@@ -871,6 +871,33 @@ int ske_rows_profile(ske_ctx *ctx, uint32_t rid, const uint8_t *lec_bytes_or_nul
                      int64_t until, int valid_filter, uint32_t sod_from, uint64_t *out_bins, uint64_t *rows_out,
                      int *complete);
 
+/* Compaction: the table's overwrite and its TTL, on the device.  A row survives
+ * when epoch >= keep_since (INT64_MIN expires nothing) and it is the
+ * last-appended row of its run of equal (lec, epoch, id) -- ske_rows_select's
+ * survivor rule.  A row below keep_since counts as expired whether or not it
+ * was also superseded.  The survivors keep their relative arrival order and
+ * occupy positions 0 .. kept - 1, so position order is still arrival order and
+ * a later append still wins over them; the compacted log depends on the log's
+ * contents and keep_since alone and is the same from run to run.
+ *   Head: used = kept; taken decreases by the rows removed, so used +
+ * refused_ids + dropped == taken holds on; refused_ids, dropped and the sticky
+ * overflow are untouched (dropped rows stay lost: a select's *complete stays 0
+ * until ske_rows_reset).
+ *   For every lecture, every window with since >= keep_since, every
+ * valid_filter and sod_from, ske_rows_select, ske_rows_group and
+ * ske_rows_profile answer after the call what they answered before it.
+ *   An empty log, or one with nothing to remove, returns kept == before and
+ * moves nothing.  A recorded append stays valid and appends at the new `used`
+ * when replayed (the head lives in the log).  Waits for the stream: SKE_EBUSY
+ * while a capture records; SKE_EINVAL for a NULL out. */
+typedef struct {
+    uint64_t before;      /* used when the call began */
+    uint64_t kept;        /* used when it returned */
+    uint64_t superseded;  /* removed: a later-appended row has the same (lec, epoch, id) */
+    uint64_t expired;     /* removed: epoch < keep_since */
+} ske_rows_compact_t;     /* before == kept + superseded + expired */
+int ske_rows_compact(ske_ctx *ctx, uint32_t rid, int64_t keep_since, ske_rows_compact_t *out);
+
 /* ---- the fused hot path (K1) ----
  * For every swipe i: v = BF.EXISTS fid id_i; if v: PFADD slot_i id_i.
  *   replaces the per-event pair attendance_processor.py:109-113 + :127-129.

@@ -152,6 +152,11 @@ class RowsInfo(C.Structure):
                 ("refused_ids", C.c_uint64), ("dropped", C.c_uint64), ("overflow", C.c_uint64)]
 
 
+class RowsCompact(C.Structure):
+    """ske_rows_compact_t (include/sketch.h)."""
+    _fields_ = [("before", C.c_uint64), ("kept", C.c_uint64), ("superseded", C.c_uint64), ("expired", C.c_uint64)]
+
+
 class RowsGroupStats(C.Structure):
     """ske_rows_group_stats_t (include/sketch.h)."""
     _fields_ = [("rows", C.c_uint64), ("n", C.c_uint64), ("sum", C.c_uint64), ("sumsq", C.c_uint64),
@@ -313,6 +318,7 @@ SIGNATURES = {
     "ske_rows_profile": (C.c_int, [_CTX, C.c_uint32, _u8p, C.c_uint32, C.c_int64, C.c_int64, C.c_int, C.c_uint32,
                                    _u64p, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "ske_rows_read": (C.c_int, [_CTX, C.c_uint32, C.c_uint64, C.c_uint64, _u64p, _vp, _vp, _u8p]),
+    "ske_rows_compact": (C.c_int, [_CTX, C.c_uint32, C.c_int64, C.POINTER(RowsCompact)]),
     "ske_swipes": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p, C.c_int]),
     "ske_swipes_async": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u8p]),
     "ske_swipes_fixed": (C.c_int, [_CTX, C.c_uint32, _u32p, _u8p, C.c_uint32, C.c_uint64, _u8p,

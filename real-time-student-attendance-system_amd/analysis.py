@@ -174,7 +174,19 @@ class StudentCounts:
     (``records``).  The id must be an integer: ``update`` takes 4- or 8-byte
     little-endian ids only, the other calls the id's canonical decimal text;
     anything else is refused and counted (``records_info()["refused_ids"]``).
-    With it set the counting calls need the swipes' times and lectures."""
+    With it set the counting calls need the swipes' times and lectures.
+
+    ``records_compact`` (default False): make room in the log instead of
+    dropping rows.  ``StudentCounts`` then keeps a host-side upper bound of the
+    log's ``used`` -- the log's own count when this object is made, plus the
+    ``n`` of every append it enqueues -- and never waits for the device on the
+    append path to learn it.  When the bound plus the next batch would pass the
+    capacity it first calls ``compact_records(records_keep_since)`` (superseded
+    rows leave, and those older than ``records_keep_since``: seconds, or
+    anything ``epoch_seconds`` takes; None expires nothing) and continues from
+    the exact ``kept``.  A batch that still does not fit is appended all the
+    same and fails open as without the option.  Replays of an append graph the
+    caller recorded bypass the bound: call ``compact_records`` after them."""
 
     def __init__(self, client, attended_key="cms:attended", invalid_key="cms:invalid",
                  error: float = 0.001, probability: float = 0.01, track_attended: int | None = None,
@@ -182,9 +194,12 @@ class StudentCounts:
                  late_from: int = 9 * 3600, track_late: int | None = None, day_profile=None,
                  lecture_counts=None, lecture_capacity_log2: int = 16, dedup=None,
                  dedup_capacity_log2: int = 22, dedup_granularity: int = 1, records=None,
-                 records_capacity_log2: int = 22):
+                 records_capacity_log2: int = 22, records_compact: bool = False, records_keep_since=None):
         self.client = client
         self._records = encode(records) if records is not None else None
+        if records_compact and records is None:
+            raise ValueError("records_compact needs records")
+        self._rec_compact, self._rec_keep = bool(records_compact), records_keep_since
         self._dedup = encode(dedup) if dedup is not None else None
         self._dedup_gran = int(dedup_granularity)
         if self._dedup_gran < 1:
@@ -233,6 +248,9 @@ class StudentCounts:
             client.seen_create(self._dedup, dedup_capacity_log2)
         if self._records is not None and self._records not in client._rows:
             client.rows_create(self._records, records_capacity_log2)
+        if self._rec_compact:  # the one wait: an existing log says where it stands
+            info = client.rows_info(self._records)
+            self._rec_cap, self._rec_bound = info["capacity"], info["used"]
 
     def _buffers(self, n: int, width: int):
         b = self._bufs
@@ -328,6 +346,7 @@ class StudentCounts:
         else:
             d_valid.from_host(np.zeros(n, np.uint8))  # BF.EXISTS of a missing key answers 0
         if self._records is not None:  # every row, with K1's answers where they are
+            self._records_room(n)
             cl.rows_enqueue(cl.rows_rid(self._records), rows[1], rows[0], fixed_ids=ids, d_valid=d_valid)
         for key, want in ((self.attended_key, 1), (self.invalid_key, 0)):
             cl.ctx.call("ske_cms_add_fixed_async", cl.cms_cid(key), C.c_void_p(d_ids.ptr), width, n,
@@ -489,6 +508,27 @@ class StudentCounts:
             raise ValueError("no records")
         return self.client.rows_info(self._records)
 
+    def compact_records(self, keep_since=None) -> dict:
+        """``client.rows_compact`` of the log: the superseded rows and those
+        older than ``keep_since`` (seconds, or anything ``epoch_seconds`` takes;
+        None: none) leave it; ``before``, ``kept``, ``superseded``, ``expired``.
+        No read of a window at or after ``keep_since`` changes its answer."""
+        if self._records is None:
+            raise ValueError("no records")
+        out = self.client.rows_compact(self._records, keep_since)
+        if self._rec_compact:
+            self._rec_bound = out["kept"]
+        return out
+
+    def _records_room(self, n: int) -> None:
+        """``records_compact``: before an append of ``n`` rows is enqueued, the
+        compaction when the bound says the batch may not fit; then the bound's step."""
+        if not self._rec_compact:
+            return
+        if self._rec_bound + n > self._rec_cap:
+            self.compact_records(self._rec_keep)
+        self._rec_bound += n
+
     def duplicate_rows(self) -> int:
         """Rows the seen set kept out of the counts so far: ``looked_at - first``."""
         if self._dedup is None:
@@ -545,6 +585,7 @@ class StudentCounts:
                         width, n, C.c_void_p(d_valid.ptr), SKE_MEM_DEVICE)
             valid = d_valid.to_host(np.uint8, n)
         if self._records is not None:  # every row, before the repeats leave
+            self._records_room(n)
             cl.rows_enqueue(cl.rows_rid(self._records), lec, ep, fixed_ids=ids, valid=valid)
         offs = (np.arange(n + 1, dtype=np.uint64) * width).astype(np.uint32)
         self._count_first(ids.reshape(-1), offs, valid, ep, lec)
@@ -629,6 +670,7 @@ class StudentCounts:
         if n == 0:
             return
         if self._records is not None:  # every row, before the repeats leave
+            self._records_room(n)
             self.client.rows_enqueue(self.client.rows_rid(self._records), lec, ep, ids=(buf, offs), valid=v)
         if self._dedup is not None:
             self._count_first(buf, offs, v, ep, lec)
@@ -683,6 +725,7 @@ class StudentCounts:
         if self._records is not None:
             # every decoded message's row from the parse columns in place: the parse's own status
             # (not the seen set's answers), the message times and K1's valid bytes
+            self._records_room(n)
             cl.ctx.call("ske_rows_append_spans_async", cl.rows_rid(self._records), msgs, cols.lec_start,
                         cols.lec_len, cols.id_start, cols.id_len, cols.status, C.c_void_p(d["epoch_all"].ptr),
                         C.c_void_p(B["valid"].ptr) if run.has_bf else None, None, n)

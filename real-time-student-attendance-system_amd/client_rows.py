@@ -16,7 +16,11 @@ pipeline in Python and is the oracle of the device's answers.
 ``rows_group`` and ``rows_profile`` count the log's rows after the upsert by
 student, by lecture or by weekday and hour, on the device -- the reference's
 ``groupby(...).size()`` calls (attendance_analysis.py:65-118), exact;
-``rows_group_oracle`` and ``rows_profile_oracle`` are their oracles."""
+``rows_group_oracle`` and ``rows_profile_oracle`` are their oracles.
+
+``rows_compact`` is the table's overwrite and TTL: the superseded rows and
+those older than a cutoff leave the log on the device, the survivors move to
+the front in arrival order; ``rows_compact_oracle`` is its oracle."""
 from __future__ import annotations
 
 import ctypes as C
@@ -26,7 +30,7 @@ import numpy as np
 
 from . import _lib
 from .encoding import encode, pack
-from .engine import DeviceBuffer, rows_group, rows_info, rows_profile, rows_read, rows_select
+from .engine import DeviceBuffer, rows_compact, rows_group, rows_info, rows_profile, rows_read, rows_select
 from .exceptions import ResponseError
 from .keyhash import murmur64a
 
@@ -107,6 +111,26 @@ def rows_oracle(batches, lecture=None, since=None, until=None, capacity=None) ->
                 np.asarray([r[2] for r in rows], np.int64), np.asarray([r[3] for r in rows], np.uint8))
 
     return {"log": cols(log), "taken": taken, "refused_ids": refused, "dropped": dropped, "select": cols(sel)}
+
+
+def rows_compact_oracle(log, keep_since=None) -> dict:
+    """``RowsMixin.rows_compact`` in pure Python over the four arrival-order
+    columns ``rows_oracle`` returns in ``"log"``: a row survives when ``epoch >=
+    keep_since`` (None: every epoch) and no later row has its (digest, epoch,
+    id); the survivors in arrival order.  Returns ``{"log": the compacted
+    columns, "kept", "superseded", "expired"}`` -- a row below the cutoff is
+    expired whether or not it was superseded."""
+    lec, ep, ids, valid = (np.asarray(c).tolist() for c in log)
+    lo = INT64_MIN if keep_since is None else int(keep_since)
+    last = {}
+    for pos, key in enumerate(zip(lec, ep, ids)):
+        if key[1] >= lo:
+            last[key] = pos  # the upsert: the last write wins
+    keep = sorted(last.values())
+    expired = sum(1 for e in ep if e < lo)
+    cols = (np.asarray([lec[p] for p in keep], np.uint64), np.asarray([ep[p] for p in keep], np.int64),
+            np.asarray([ids[p] for p in keep], np.int64), np.asarray([valid[p] for p in keep], np.uint8))
+    return {"log": cols, "kept": len(keep), "superseded": len(ep) - expired - len(keep), "expired": expired}
 
 
 def _counted(rows, valid, late_from):
@@ -297,6 +321,19 @@ class RowsMixin:
         self._rows_out = cols
         return {"lecture_digest": cols[0][:n].copy(), "epoch": cols[1][:n].copy(), "student_id": cols[2][:n].copy(),
                 "is_valid": cols[3][:n].copy(), "complete": complete}
+
+    def rows_compact(self, name, keep_since=None) -> dict:
+        """Drop the log's dead rows on the device (``ske_rows_compact``): those
+        a later row with the same (lecture, time, id) superseded and those with
+        ``time < keep_since`` (seconds, or anything ``analysis.epoch_seconds``
+        takes; None expires nothing).  The survivors keep their arrival order
+        at positions ``0 .. kept - 1``; ``used`` and ``taken`` follow, the
+        sticky ``overflow`` stays.  Returns ``{"before", "kept", "superseded",
+        "expired"}``.  No ``rows_select``, ``rows_group`` or ``rows_profile``
+        over a window with ``since >= keep_since`` changes its answer."""
+        from .analysis import epoch_seconds
+        lo = INT64_MIN if keep_since is None else int(epoch_seconds([keep_since])[0])
+        return rows_compact(self.ctx, self.rows_rid(name), lo)
 
     def rows_read(self, name) -> dict:
         """The raw log in arrival order (a checkpoint): the four columns."""

@@ -1,6 +1,6 @@
 // sketch_api_rows.cpp -- libsketch C-ABI (include/sketch.h): row logs, the
 // attendance table's rows in arrival order (init, reset, info, the three
-// appends, select, group, profile, read), kernels in sketch_rows.hip.  A log is one device
+// appends, select, group, profile, compact, read), kernels in sketch_rows.hip.  A log is one device
 // allocation owned by the context and addressed by rid.
 #include <stddef.h>
 #include <string.h>
@@ -20,7 +20,9 @@ static_assert(SKE_ROWS_BY_STUDENT == kRowsByStudent && SKE_ROWS_BY_LECTURE == kR
                   SKE_ROWS_VALID_ANY == kRowsValidAny && SKE_ROWS_VALID_ONLY == kRowsValidOnly &&
                   SKE_ROWS_INVALID_ONLY == kRowsInvalidOnly,
               "the group-by's selectors as sketch.h states them");
-static_assert(sizeof(ske_rows_group_stats_t) == 64 && SKE_TP_BINS == kTpBins, "eight u64 words; the profile's bins");
+static_assert(sizeof(ske_rows_compact_t) == 32 && sizeof(RowsCompactCounts) == sizeof(ske_rows_compact_t),
+              "four u64 words");
+static_assert(sizeof(ske_rows_group_stats_t) == 64&& SKE_TP_BINS == kTpBins, "eight u64 words; the profile's bins");
 
 namespace {
 
@@ -398,6 +400,47 @@ int ske_rows_select(ske_ctx *c, uint32_t rid, const uint8_t *lec_bytes, uint32_t
         HIPCHK(c, hipMemcpyAsync(out_id, d_id, uint64_t(runs) * 8, hipMemcpyDeviceToHost, c->st));
         HIPCHK(c, hipMemcpyAsync(out_valid, d_valid, runs, hipMemcpyDeviceToHost, c->st));
     }
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SKE_OK;
+}
+
+int ske_rows_compact(ske_ctx *c, uint32_t rid, int64_t keep_since, ske_rows_compact_t *out) {
+    if (!c || !out) return SKE_EINVAL;
+    int rc = SKE_OK;
+    Rows *R = obj_for_sync_call(c, kRowsFamily, c->rows, rid, "ske_rows_compact", &rc);
+    if (!R) return rc;
+    memset(out, 0, sizeof *out);
+    RowsHead h{};
+    rc = obj_read_head(c, *R, &h, sizeof h);
+    if (rc) return rc;
+    const uint32_t used = uint32_t(h.used);  // <= 2^28
+    // the select's own survivor rule, over every lecture from the cutoff on
+    RowsFront F{};
+    int complete = 1;
+    rc = rows_front(c, *R, nullptr, 0, keep_since, INT64_MAX, false, &complete, &F);
+    if (rc) return rc;
+    const RowsCompactCounts n = rows_compact_counts(used, F.m, F.runs);
+    out->before = n.before;
+    out->kept = n.kept;
+    out->superseded = n.superseded;
+    out->expired = n.expired;
+    if (n.kept == n.before) return SKE_OK;  // nothing to remove: no launch
+
+    const uint32_t kept = uint32_t(n.kept);
+    RowsCompactWork K{};
+    if (kept) {
+        hipError_t e = hipSuccess;
+        K.keep = (uint8_t *)scratch_get(c->scratch, kScrRowsKeep, used, &e);
+        if (e != hipSuccess) return scratch_error(c, e);
+        K.cnt = (uint32_t *)scratch_get(c->scratch, kScrRowsKeepCnt, rows_cnt_bytes(used), &e);
+        if (e != hipSuccess) return scratch_error(c, e);
+        // the sort is over: its key buffers (m >= kept words each) carry the survivors
+        K.tmp_a = scratch_get(c->scratch, kScrKeysOrFirst, uint64_t(F.m) * 8, &e);
+        if (e != hipSuccess) return scratch_error(c, e);
+        K.tmp_b = scratch_get(c->scratch, kScrKeysSorted, uint64_t(F.m) * 8, &e);
+        if (e != hipSuccess) return scratch_error(c, e);
+    }
+    HIPCHK(c, launch_rows_compact(log_of(*R), used, F.pos, F.m, F.W, kept, K, unsigned(c->rows_grid), c->cus, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     return SKE_OK;
 }

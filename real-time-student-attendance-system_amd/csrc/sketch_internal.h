@@ -3,6 +3,7 @@
 #include <cstddef>
 
 #include "sketch_common.h"
+#include "sketch_rows_compact.h"
 #include "sketch_rows_group.h"
 
 namespace ske {
@@ -532,6 +533,19 @@ hipError_t launch_rows_grp_out(const RowsGrpWork &G, uint32_t n, unsigned long l
 // D->bins[tp_bin] += the counted survivors (after launch_rows_last)
 hipError_t launch_rows_profile(const RowsLog &L, const uint32_t *pos, uint32_t m, int valid_filter, uint32_t sod_from,
                                const RowsWork &W, RowsGrpDev *D, unsigned grid, int cus, hipStream_t st);
+// The compaction (DESIGN.md "Row log compaction"; the arithmetic is
+// sketch_rows_compact.h's), after launch_rows_last over the whole log from the
+// cutoff on (W.flag = survivor per sorted position, `kept` of them among m).
+struct RowsCompactWork {
+    uint8_t *keep;  // used bytes: 1 at a survivor's log position
+    uint32_t *cnt;  // rows_cnt_bytes(used): the keep bytes' tile counts, scanned in place
+    void *tmp_a;    // 8 * kept bytes each: a pair of log columns' survivors on their way to the front
+    void *tmp_b;
+};
+// the survivors of positions [0, used) to [0, kept) in position order, then the head: used = kept, taken
+// less the rows removed.  kept == 0 launches the head's kernel alone.
+hipError_t launch_rows_compact(const RowsLog &L, uint32_t used, const uint32_t *pos, uint32_t m, const RowsWork &W,
+                               uint32_t kept, const RowsCompactWork &K, unsigned grid, int cus, hipStream_t st);
 // stable radix sort of (key, pos) pairs by key, signed or unsigned 64 bits (sketch_order.hip; the
 // temporary is kScrSortTmp)
 hipError_t rows_sort_pairs(Scratch *s, bool is_signed, const unsigned long long *keys, unsigned long long *keys_s,
@@ -619,6 +633,8 @@ enum ScratchSlot : int {
     kScrRowsGrpCnt,    //   the three tile-count arrays (counted, group ends, listed groups),
     kScrRowsGrpEnds,   //   the counted prefix at each group's end,
     kScrRowsGrpCounts, //   the listed groups' counts (u32), which the median select reads
+    kScrRowsKeep,      // ske_rows_compact: a keep byte per log position,
+    kScrRowsKeepCnt,   //   the totals and the per-tile counts of the keep bytes
     // -- xr
     kScrXr,            // launch_k1: the XCD-partitioned K1's state (sketch_xr.hip)
     kScrPartRec,       // part_scratch (sketch_part.hip): probe records,

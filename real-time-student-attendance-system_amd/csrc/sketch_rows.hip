@@ -474,6 +474,69 @@ __global__ void __launch_bounds__(kRowsBlock) k_rows_profile(const RowsLog L, co
         if (s_b[i]) atomicAdd(&D->bins[i], (unsigned long long)s_b[i]);
 }
 
+// ---- compaction (the arithmetic is sketch_rows_compact.h's)
+//
+// After the front end over the whole log (every lecture, epoch >= keep_since,
+// table order) flagged each run's survivor per sorted position:
+//   k_rows_ckeep   per sorted position: a survivor's log position gets its keep
+//                  byte (the bytes were cleared)
+//   k_rows_ccount  per tile of log positions: the count of keep bytes
+//   k_rows_scan    the tile counts to their prefixes
+//   k_rows_cmove   two columns a launch: the survivor at position i to
+//                  prefix[tile] + rank in tile of two scratch columns
+//   k_rows_cback   the scratch columns' [0, kept) back over the log's
+//   k_rows_cend    one thread: the head
+// A launch that reads the log writes scratch only, and the other way round, so
+// no workgroup reads a log location another of its launch writes.  The target of
+// a survivor is a function of the keep bytes alone: position order stays arrival
+// order and the compacted log is the same from run to run.
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_ckeep(const uint32_t *pos, uint32_t m, const uint8_t *surv,
+                                                            uint8_t *keep) {
+    const uint64_t stride = uint64_t(gridDim.x) * kRowsBlock;
+    for (uint64_t j = uint64_t(blockIdx.x) * kRowsBlock + threadIdx.x; j < m; j += stride)
+        if (surv[j] == 1) keep[pos[j]] = 1;
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_ccount(const uint8_t *keep, uint32_t used, uint32_t *cnt) {
+    __shared__ unsigned int s_ok[kRowsWaves], s_ref[kRowsWaves];
+    const uint64_t tiles = rows_tiles(used);
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t i = t * kRowsBlock + threadIdx.x;
+        rows_tile_count(i < used && keep[i] == 1, false, cnt, tiles, t, s_ok, s_ref);
+    }
+}
+
+template <typename A, typename B>
+__global__ void __launch_bounds__(kRowsBlock) k_rows_cmove(const A *a, const B *b, uint32_t used, const uint8_t *keep,
+                                                            const uint32_t *cnt, A *out_a, B *out_b) {
+    __shared__ unsigned int s_ok[kRowsWaves];
+    const uint64_t tiles = rows_tiles(used);
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t i = t * kRowsBlock + threadIdx.x;
+        const bool ok = i < used && keep[i] == 1;
+        const uint32_t rank = rows_tile_rank(ok, s_ok);
+        if (!ok) continue;
+        const uint64_t o = uint64_t(cnt[4 + t]) + rank;
+        out_a[o] = a[i];
+        out_b[o] = b[i];
+    }
+}
+
+template <typename A, typename B>
+__global__ void __launch_bounds__(kRowsBlock) k_rows_cback(const A *a, const B *b, uint32_t kept, A *out_a, B *out_b) {
+    const uint64_t stride = uint64_t(gridDim.x) * kRowsBlock;
+    for (uint64_t i = uint64_t(blockIdx.x) * kRowsBlock + threadIdx.x; i < kept; i += stride) {
+        out_a[i] = a[i];
+        out_b[i] = b[i];
+    }
+}
+
+__global__ void k_rows_cend(const RowsLog L, unsigned long long kept) {
+    if (blockIdx.x || threadIdx.x) return;
+    rows_compact_head(&L.head->used, &L.head->taken, kept);
+}
+
 // workgroups of a kernel over n items: the context's override, else eight per CU
 unsigned grid_of(uint64_t n, unsigned grid, int cus) {
     return grid_for(n, kRowsBlock, grid, unsigned(cus) * 8, kRowsMaxGrid);
@@ -498,7 +561,47 @@ hipError_t rows_append_kind(const RowsLog &L, const RowsItems &I, const RowsWork
     return hipGetLastError();
 }
 
+// the survivors of two log columns to the front, by way of the two scratch columns
+template <typename A, typename B>
+hipError_t rows_compact_pair(A *a, B *b, uint32_t used, uint32_t kept, const RowsCompactWork &K, unsigned g,
+                             unsigned g_kept, hipStream_t st) {
+    A *ta = reinterpret_cast<A *>(K.tmp_a);
+    B *tb = reinterpret_cast<B *>(K.tmp_b);
+    hipLaunchKernelGGL((k_rows_cmove<A, B>), dim3(g), dim3(kRowsBlock), 0, st, (const A *)a, (const B *)b, used,
+                       (const uint8_t *)K.keep, (const uint32_t *)K.cnt, ta, tb);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_rows_cback<A, B>), dim3(g_kept), dim3(kRowsBlock), 0, st, (const A *)ta, (const B *)tb, kept,
+                       a, b);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t launch_rows_compact(const RowsLog &L, uint32_t used, const uint32_t *pos, uint32_t m, const RowsWork &W,
+                               uint32_t kept, const RowsCompactWork &K, unsigned grid, int cus, hipStream_t st) {
+    if (kept > 0) {
+        const unsigned g = grid_of(used, grid, cus);
+        hipError_t e = hipMemsetAsync(K.keep, 0, used, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_rows_ckeep, dim3(grid_of(m, grid, cus)), dim3(kRowsBlock), 0, st, pos, m,
+                           (const uint8_t *)W.flag, K.keep);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_rows_ccount, dim3(g), dim3(kRowsBlock), 0, st, (const uint8_t *)K.keep, used, K.cnt);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        e = rows_scan(K.cnt, used, st);
+        if (e != hipSuccess) return e;
+        const unsigned g_kept = grid_of(kept, grid, cus);
+        e = rows_compact_pair(L.lec, L.epoch, used, kept, K, g, g_kept, st);
+        if (e != hipSuccess) return e;
+        e = rows_compact_pair(L.id, L.valid, used, kept, K, g, g_kept, st);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_rows_cend, dim3(1), dim3(64), 0, st, L, (unsigned long long)kept);
+    return hipGetLastError();
+}
 
 hipError_t launch_rows_append(const RowsLog &L, const RowsItems &I, const RowsWork &W, unsigned grid, int cus,
                               hipStream_t st) {

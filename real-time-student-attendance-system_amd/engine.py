@@ -14,8 +14,8 @@ import gc
 import numpy as np
 
 from ._lib import (CmsInfo, Context, GenParams, HhInfo, HhStats, IngestDense, SKE_HH_ID_BYTES, SKE_HLL_DUMP_CARD,
-                   SKE_MEM_DEVICE, SKE_MEM_HOST, SKE_TALLY_KEY_BYTES, SKE_TP_BINS, RowsGroupStats, RowsInfo, SeenInfo,
-                   SKE_EROWSSPACE, SketchLibError, TallyInfo)
+                   SKE_MEM_DEVICE, SKE_MEM_HOST, SKE_TALLY_KEY_BYTES, SKE_TP_BINS, RowsCompact, RowsGroupStats,
+                   RowsInfo, SeenInfo, SKE_EROWSSPACE, SketchLibError, TallyInfo)
 from . import synthetic
 
 PASS_KINDS = 9  # SKE_PASS_KINDS (include/sketch.h)
@@ -250,6 +250,15 @@ def rows_info(ctx: Context, rid: int) -> dict:
     info = RowsInfo()
     ctx.call("ske_rows_info", int(rid), C.byref(info))
     return {k: int(getattr(info, k)) for k, _ in RowsInfo._fields_}
+
+
+def rows_compact(ctx: Context, rid: int, keep_since: int) -> dict:
+    """ske_rows_compact: the superseded rows and those with ``epoch <
+    keep_since`` leave the log, the survivors move to the front in arrival
+    order; ``before``, ``kept``, ``superseded`` and ``expired`` as Python ints."""
+    out = RowsCompact()
+    ctx.call("ske_rows_compact", int(rid), int(keep_since), C.byref(out))
+    return {k: int(getattr(out, k)) for k, _ in RowsCompact._fields_}
 
 
 def rows_read(ctx: Context, rid: int, first: int, n: int):

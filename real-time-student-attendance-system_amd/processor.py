@@ -232,6 +232,15 @@ class AttendanceProcessor:
                  "is_valid": bool(v)}
                 for d, e, i, v in zip(rec["lecture_digest"], rec["epoch"], rec["student_id"], rec["is_valid"])]
 
+    def compact_records(self, keep_since=None) -> dict:
+        """The table's overwrite and TTL over the row log
+        (``StudentCounts.compact_records``): redelivered rows' earlier copies and
+        the rows older than ``keep_since`` leave it; ``before``, ``kept``,
+        ``superseded``, ``expired``.  ValueError without ``records``."""
+        if not getattr(self.counts, "keeps_records", False):
+            raise ValueError("compact_records needs a StudentCounts with records")
+        return self.counts.compact_records(keep_since)
+
     def _unique_attendees(self, lecture_id: str, day: str | None) -> int:
         prefix = self.config.hll_key_prefix
         if self.config.hll_key_form == "code":
