@@ -870,6 +870,44 @@ int ske_rows_group(ske_ctx *ctx, uint32_t rid, int by, const uint8_t *lec_bytes_
 int ske_rows_profile(ske_ctx *ctx, uint32_t rid, const uint8_t *lec_bytes_or_null, uint32_t lec_len, int64_t since,
                      int64_t until, int valid_filter, uint32_t sod_from, uint64_t *out_bins, uint64_t *rows_out,
                      int *complete);
+/* Group merge: many (key, count) lists summed into one -- what joins the
+ * ske_rows_group outputs of several contexts (ranks that each hold the rows of
+ * the lectures they own) into the group-by of all their rows.  It needs no log:
+ * it works on caller arrays and context scratch.
+ *   keys[i], counts[i], i < n_in: entries in any order, the same key any number
+ * of times (the intended input is several ske_rows_group outputs end to end,
+ * but no order is required); mem says where these two arrays and the two
+ * output arrays are.  The inputs are not modified; inputs and outputs must not
+ * overlap.
+ *   The merged count of a key is the sum of its entries' counts; a key is
+ * listed when that sum is nonzero, so zero-count entries are padding that
+ * vanishes.  out_key[g], out_count[g] = the listed keys ascending -- by =
+ * SKE_ROWS_BY_LECTURE unsigned, SKE_ROWS_BY_STUDENT signed, ske_rows_group's
+ * order -- and their sums.  *stats is over the listed sums, each field as
+ * ske_rows_group defines it, except stats->rows, which is written 0 (the caller
+ * sums the parts' rows).  *multi_out = the listed keys that received more than
+ * one entry with a nonzero count.  *n_out (= stats->n), *stats and *multi_out
+ * are always written.
+ *   Capacity: ske_rows_group's protocol.  More listed keys than cap:
+ * SKE_EROWSSPACE with no output array touched; cap = 0 (both arrays may be NULL
+ * then) is the statistics alone and succeeds when nothing is listed.
+ *   n_in == 0: SKE_OK with everything zero.  SKE_EINVAL: an unknown by; a NULL
+ * n_out, stats or multi_out; NULL inputs with n_in > 0; n_in > 2^28; a total of
+ * the counts above 2^32 - 1 (which keeps every prefix in 32 bits and sumsq in
+ * 64, as "sum <= 2^28" does for ske_rows_group) -- the total is found on the
+ * device and looked at before any output is written.  Waits for the stream:
+ * SKE_EBUSY while a capture records.
+ *   Integer arithmetic throughout: the answer is the same from run to run and
+ * does not depend on the order of the entries.
+ *   Identity: merging the output of one ske_rows_group call alone returns it
+ * unchanged -- the keys, the counts and every statistic except rows -- with
+ * *multi_out == 0.
+ *   Additivity: when every (lecture, epoch, id) lies in one part only -- rows
+ * sharded by lecture -- the merge of the parts' ske_rows_group outputs is the
+ * ske_rows_group of all the rows in one log, for either by and every filter. */
+int ske_rows_group_merge(ske_ctx *ctx, int by, const uint64_t *keys, const uint64_t *counts, uint64_t n_in,
+                         uint64_t *out_key, uint64_t *out_count, uint64_t cap, uint64_t *n_out,
+                         ske_rows_group_stats_t *stats, uint64_t *multi_out, int mem);
 
 /* Compaction: the table's overwrite and its TTL, on the device.  A row survives
  * when epoch >= keep_since (INT64_MIN expires nothing) and it is the

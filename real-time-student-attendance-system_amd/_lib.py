@@ -315,6 +315,9 @@ SIGNATURES = {
     "ske_rows_group": (C.c_int, [_CTX, C.c_uint32, C.c_int, _u8p, C.c_uint32, C.c_int64, C.c_int64, C.c_int,
                                  C.c_uint32, _u64p, _u64p, C.c_uint64, C.POINTER(C.c_uint64),
                                  C.POINTER(RowsGroupStats), C.POINTER(C.c_int), C.c_int]),
+    "ske_rows_group_merge": (C.c_int, [_CTX, C.c_int, _u64p, _u64p, C.c_uint64, _u64p, _u64p, C.c_uint64,
+                                       C.POINTER(C.c_uint64), C.POINTER(RowsGroupStats), C.POINTER(C.c_uint64),
+                                       C.c_int]),
     "ske_rows_profile": (C.c_int, [_CTX, C.c_uint32, _u8p, C.c_uint32, C.c_int64, C.c_int64, C.c_int, C.c_uint32,
                                    _u64p, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "ske_rows_read": (C.c_int, [_CTX, C.c_uint32, C.c_uint64, C.c_uint64, _u64p, _vp, _vp, _u8p]),

@@ -119,6 +119,61 @@ def reference_rule(stats: dict, rule: str):
     return (x + twice_median + 1) // 2
 
 
+def exact_by_day_format(bins) -> dict:
+    """``{day name: rows}`` of the weekdays that have any, in the order of the
+    names, from the ``[7, 24]`` (or 168) weekday-by-hour bins of the log's rows."""
+    per_day = np.asarray(bins).reshape(7, 24).sum(axis=1)
+    return {d: int(per_day[i]) for d, i in sorted((d, i) for i, d in enumerate(DAY_NAMES)) if per_day[i]}
+
+
+def exact_rankings_format(g: dict, names, k: int = 3) -> dict:
+    """The by-lecture group-by ``g`` as ``lecture_rankings`` writes it: the
+    digests joined to the tally listing's ``names`` (a digest none of them has
+    shows as ``"#<hex digest>"``), count descending, name ascending; carries
+    ``g``'s ``complete``."""
+    from .client_rows import lecture_digest
+    by_digest = {lecture_digest(key): key.decode("utf-8", "replace") for key in names}
+    ranked = sorted((-int(c), by_digest.get(int(d), "#%016x" % int(d))) for d, c in zip(g["keys"], g["counts"]))
+    k = int(k)
+    return {"most_attended": {name: -c for c, name in ranked[:k]},
+            "least_attended": {name: -c for c, name in ranked[max(len(ranked) - k, 0):]} if k > 0 else {},
+            "complete": g["complete"]}
+
+
+def exact_insight_entries(late: dict, by_day: dict, ranks, att: dict, inv: dict, late_from: int) -> list:
+    """The five exact entries from their answers: the per-student group-bys of
+    the late, of all and of the invalid rows (``rows_group``'s dicts), the
+    ``{day name: rows}`` dict and the rankings (None: no lecture entry).  One
+    context (``StudentCounts.exact_insights``) and the ranks' merge
+    (``distributed.ShardedCounts.exact_insights``) both end here.  An entry
+    carries its answer's ``complete`` and, where the answer has one, its
+    ``split_lectures``."""
+    def marks(src):
+        return {key: src[key] for key in ("complete", "split_lectures") if key in src}
+
+    twice = late["stats"]["med_lo"] + late["stats"]["med_hi"]
+    data = {int(i): int(c) for i, c in zip(late["keys"], late["counts"]) if 2 * int(c) > twice}
+    out = [{"title": "Habitual Latecomers",
+            "description": f"Found {len(data)} students who frequently arrive after {late_from // 3600}:00 AM",
+            "data": data, **marks(late)},
+           {"title": "Attendance by Day", "description": "Distribution of attendance across different days",
+            "data": by_day, **marks(late)}]
+    if ranks is not None:
+        out.append({"title": "Lecture Attendance Rankings", "description": "Most and least attended lectures",
+                    "data": {"most_attended": ranks["most_attended"], "least_attended": ranks["least_attended"]},
+                    **marks(ranks)})
+    thr = reference_rule(att["stats"], "median+std")
+    out.append({"title": "Most Consistent Attendees",
+                "description": "Students whose estimated attendance reaches the threshold",
+                "data": {int(i): int(c) for i, c in zip(att["keys"], att["counts"])
+                         if thr is not None and int(c) >= thr},
+                **marks(att)})
+    out.append({"title": "Invalid Attendance Attempts",
+                "description": "Estimated invalid attendance attempts by student id",
+                "data": {int(i): int(c) for i, c in zip(inv["keys"], inv["counts"])}, **marks(inv)})
+    return out
+
+
 class StudentCounts:
     """Attended / invalid swipe counts per student id, as two CMS keys of a
     ``SketchClient``.
@@ -440,8 +495,7 @@ class StudentCounts:
         name: rows}`` of the weekdays that have any, in the order of the names."""
         if self._records is None:
             raise ValueError("no records")
-        per_day = self.client.rows_profile(self._records).sum(axis=1)
-        return {d: int(per_day[i]) for d, i in sorted((d, i) for i, d in enumerate(DAY_NAMES)) if per_day[i]}
+        return exact_by_day_format(self.client.rows_profile(self._records))
 
     def exact_lecture_rankings(self, k: int = 3) -> dict:
         """``lecture_rankings`` from the log's rows: ``client.rows_group`` by
@@ -453,15 +507,8 @@ class StudentCounts:
             raise ValueError("no records")
         if self._lectures is None:
             raise ValueError("exact_lecture_rankings needs lecture_counts (the lecture names)")
-        from .client_rows import lecture_digest
         names, *_ = self.client.tally_list(self._lectures)
-        by_digest = {lecture_digest(key): key.decode("utf-8", "replace") for key in names}
-        g = self.client.rows_group(self._records, "lecture")
-        ranked = sorted((-int(c), by_digest.get(int(d), "#%016x" % int(d))) for d, c in zip(g["keys"], g["counts"]))
-        k = int(k)
-        return {"most_attended": {name: -c for c, name in ranked[:k]},
-                "least_attended": {name: -c for c, name in ranked[max(len(ranked) - k, 0):]} if k > 0 else {},
-                "complete": g["complete"]}
+        return exact_rankings_format(self.client.rows_group(self._records, "lecture"), names, k)
 
     def exact_insights(self, lecture_k: int | None = 3) -> list:
         """The reference's five insights (attendance_analysis.py:65-118) in its
@@ -474,32 +521,10 @@ class StudentCounts:
         every entry carries the log's ``complete``.  ``lecture_k=None`` leaves
         the lecture entry out (it needs ``lecture_counts``)."""
         late = self.exact_counts("late")
-        twice = late["stats"]["med_lo"] + late["stats"]["med_hi"]
-        data = {int(i): int(c) for i, c in zip(late["keys"], late["counts"]) if 2 * int(c) > twice}
-        out = [{"title": "Habitual Latecomers",
-                "description": f"Found {len(data)} students who frequently arrive after "
-                               f"{self.late_from // 3600}:00 AM",
-                "data": data, "complete": late["complete"]},
-               {"title": "Attendance by Day", "description": "Distribution of attendance across different days",
-                "data": self.exact_by_day(), "complete": late["complete"]}]
-        if lecture_k is not None:
-            ranks = self.exact_lecture_rankings(lecture_k)
-            out.append({"title": "Lecture Attendance Rankings", "description": "Most and least attended lectures",
-                        "data": {"most_attended": ranks["most_attended"], "least_attended": ranks["least_attended"]},
-                        "complete": ranks["complete"]})
-        att = self.exact_counts("attended")
-        thr = reference_rule(att["stats"], "median+std")
-        out.append({"title": "Most Consistent Attendees",
-                    "description": "Students whose estimated attendance reaches the threshold",
-                    "data": {int(i): int(c) for i, c in zip(att["keys"], att["counts"])
-                             if thr is not None and int(c) >= thr},
-                    "complete": att["complete"]})
-        inv = self.exact_counts("invalid")
-        out.append({"title": "Invalid Attendance Attempts",
-                    "description": "Estimated invalid attendance attempts by student id",
-                    "data": {int(i): int(c) for i, c in zip(inv["keys"], inv["counts"])},
-                    "complete": inv["complete"]})
-        return out
+        by_day = self.exact_by_day()
+        ranks = self.exact_lecture_rankings(lecture_k) if lecture_k is not None else None
+        return exact_insight_entries(late, by_day, ranks, self.exact_counts("attended"),
+                                     self.exact_counts("invalid"), self.late_from)
 
     def records_info(self) -> dict:
         """``client.rows_info`` of the log: capacity, used, taken, refused_ids,

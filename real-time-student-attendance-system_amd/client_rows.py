@@ -17,6 +17,9 @@ pipeline in Python and is the oracle of the device's answers.
 student, by lecture or by weekday and hour, on the device -- the reference's
 ``groupby(...).size()`` calls (attendance_analysis.py:65-118), exact;
 ``rows_group_oracle`` and ``rows_profile_oracle`` are their oracles.
+``rows_group_merge`` sums several such group lists -- the ranks' of a run
+sharded by lecture -- into the list of all their rows, on the device
+(``ske_rows_group_merge``); ``rows_group_merge_oracle`` is its oracle.
 
 ``rows_compact`` is the table's overwrite and TTL: the superseded rows and
 those older than a cutoff leave the log on the device, the survivors move to
@@ -30,7 +33,8 @@ import numpy as np
 
 from . import _lib
 from .encoding import encode, pack
-from .engine import DeviceBuffer, rows_compact, rows_group, rows_info, rows_profile, rows_read, rows_select
+from .engine import (DeviceBuffer, rows_compact, rows_group, rows_group_merge, rows_info, rows_profile, rows_read,
+                     rows_select)
 from .exceptions import ResponseError
 from .keyhash import murmur64a
 
@@ -175,6 +179,39 @@ def rows_group_oracle(batches, by="student", lecture=None, since=None, until=Non
     stats["rows"] = int(sel[1].size)
     return {"keys": np.asarray(keys, np.int64 if by == "student" else np.uint64),
             "counts": np.asarray([groups[k] for k in keys], np.uint64), "stats": stats}
+
+
+def rows_group_merge_oracle(parts, by="student") -> dict:
+    """``RowsMixin.rows_group_merge`` in pure Python.  ``parts``: a list of
+    ``rows_group`` / ``rows_group_oracle`` results (``keys``, ``counts`` and,
+    where present, ``stats["rows"]``).  A key's merged count is the sum of its
+    entries' counts; the keys with a nonzero sum come out ascending, int64 by
+    student, uint64 by lecture.  ``stats`` is ``group_stats`` of the sums with
+    ``rows`` the sum of the parts' ``rows``; ``multi`` the listed keys that
+    more than one entry with a nonzero count fed.  Refuses what the device
+    call refuses: a count above 2^32 - 1, or a total above it."""
+    if by not in ("student", "lecture"):
+        raise ValueError('by is "student" or "lecture"')
+    sums: dict[int, int] = {}
+    fed: dict[int, int] = {}
+    total = rows = 0
+    for p in parts:
+        rows += int(p.get("stats", {}).get("rows", 0))
+        for k, c in zip(np.asarray(p["keys"]).tolist(), np.asarray(p["counts"]).tolist()):
+            k, c = int(k), int(c)
+            if c > 0xFFFFFFFF:
+                raise ValueError("a count above 2^32 - 1")
+            total += c
+            sums[k] = sums.get(k, 0) + c
+            fed[k] = fed.get(k, 0) + (c != 0)
+    if total > 0xFFFFFFFF:
+        raise ValueError("the counts' total is above 2^32 - 1")
+    keys = sorted(k for k, c in sums.items() if c)
+    stats = group_stats(sums[k] for k in keys)
+    stats["rows"] = rows
+    return {"keys": np.asarray(keys, np.int64 if by == "student" else np.uint64),
+            "counts": np.asarray([sums[k] for k in keys], np.uint64), "stats": stats,
+            "multi": sum(1 for k in keys if fed[k] > 1)}
 
 
 def rows_profile_oracle(batches, lecture=None, since=None, until=None, valid=None, late_from=None,
@@ -384,3 +421,39 @@ class RowsMixin:
         (``ske_rows_profile``): a ``[7, 24]`` uint64 array."""
         lec, lo, hi, vf, sod = self._rows_window(lecture, since, until, valid, late_from)
         return rows_profile(self.ctx, self.rows_rid(name), lec, lo, hi, vf, sod)[0]
+
+    def rows_group_merge(self, by, keys, counts, groups: bool = True) -> dict:
+        """Several group lists summed into one on the device
+        (``ske_rows_group_merge``): ``keys`` and ``counts`` are host numpy
+        arrays of (key, count) entries in any order -- ``rows_group`` results
+        end to end, say -- the same key any number of times.  Returns
+        ``{"keys", "counts", "stats", "multi"}``: the keys whose counts sum to
+        more than zero, ascending and typed as ``rows_group`` types them (int64
+        student ids, uint64 lecture digests), their sums (uint64), ``stats`` as
+        ``rows_group`` gives them with ``median`` added and ``rows`` 0 (the
+        caller sums the parts' rows), and ``multi``, the listed keys that more
+        than one entry with a nonzero count fed.  No count and no total may
+        pass 2^32 - 1 (``ValueError``).  ``groups`` False: the statistics alone."""
+        if by not in ("student", "lecture"):
+            raise ValueError('by is "student" or "lecture"')
+        student = by == "student"
+        k, c = np.asarray(keys), np.asarray(counts)
+        if k.ndim != 1 or k.shape != c.shape:
+            raise ValueError("one count per key")
+        if k.size and (k.dtype.kind not in "iu" or c.dtype.kind not in "iu"):
+            raise ValueError("keys and counts are integers")
+        if c.size and c.dtype.kind == "i" and int(c.min()) < 0:
+            raise ValueError("a count is not negative")
+        if k.size > 1 << 28:
+            raise ValueError("at most 2^28 entries")
+        k = np.ascontiguousarray(k.astype(np.int64 if k.dtype.kind == "i" else np.uint64, copy=False)).view(np.uint64)
+        c = np.ascontiguousarray(c.astype(np.uint64, copy=False))
+        # below 2^28 entries of at most 2^32 - 1 each: the uint64 sum cannot wrap
+        if c.size and (int(c.max()) > 0xFFFFFFFF or int(c.sum(dtype=np.uint64)) > 0xFFFFFFFF):
+            raise ValueError("no count and no total above 2^32 - 1")
+        out_k, out_c, stats, multi = rows_group_merge(
+            self.ctx, _lib.SKE_ROWS_BY_STUDENT if student else _lib.SKE_ROWS_BY_LECTURE, k, c, k.size,
+            _lib.SKE_MEM_HOST, groups)
+        stats["median"] = (stats["med_lo"] + stats["med_hi"]) / 2
+        return {"keys": out_k.view(np.int64).copy() if student else out_k.copy(), "counts": out_c.copy(),
+                "stats": stats, "multi": multi}

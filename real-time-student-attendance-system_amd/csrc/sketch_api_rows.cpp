@@ -1,7 +1,8 @@
 // sketch_api_rows.cpp -- libsketch C-ABI (include/sketch.h): row logs, the
 // attendance table's rows in arrival order (init, reset, info, the three
 // appends, select, group, profile, compact, read), kernels in sketch_rows.hip.  A log is one device
-// allocation owned by the context and addressed by rid.
+// allocation owned by the context and addressed by rid.  ske_rows_group_merge, which sums several
+// group-bys' outputs, needs no log: caller arrays and context scratch.
 #include <stddef.h>
 #include <string.h>
 
@@ -521,6 +522,128 @@ int ske_rows_group(ske_ctx *c, uint32_t rid, int by, const uint8_t *lec_bytes, u
     }
     HIPCHK(c, hipStreamSynchronize(c->st));
     *n_out = n;
+    stats->n = h.n;
+    stats->sum = h.sum;
+    stats->sumsq = h.sumsq;
+    stats->min = h.min;
+    stats->max = h.max;
+    stats->med_lo = h.sel.prefix[0];
+    stats->med_hi = h.sel.prefix[1];
+    return fits ? SKE_OK : SKE_EROWSSPACE;
+}
+
+int ske_rows_group_merge(ske_ctx *c, int by, const uint64_t *keys, const uint64_t *counts, uint64_t n_in,
+                         uint64_t *out_key, uint64_t *out_count, uint64_t cap, uint64_t *n_out,
+                         ske_rows_group_stats_t *stats, uint64_t *multi_out, int mem) {
+    if (!c || !n_out || !stats || !multi_out) return SKE_EINVAL;
+    *n_out = 0;
+    *multi_out = 0;
+    memset(stats, 0, sizeof *stats);
+    if (by != SKE_ROWS_BY_STUDENT && by != SKE_ROWS_BY_LECTURE) return SKE_EINVAL;
+    if (c->capturing) {
+        c->last_hip = "ske_rows_group_merge waits for the stream and cannot be recorded";
+        return SKE_EBUSY;
+    }
+    if (n_in > kRowsMergeMaxEntries) return SKE_EINVAL;
+    if (n_in && (!keys || !counts)) return SKE_EINVAL;
+    if (cap && (!out_key || !out_count)) return SKE_EINVAL;
+    if (n_in == 0) return SKE_OK;
+    const uint32_t m = uint32_t(n_in);
+    const unsigned grid = unsigned(c->rows_grid);
+    int rc = SKE_OK;
+
+    const unsigned long long *d_keys = (const unsigned long long *)keys;
+    const unsigned long long *d_counts = (const unsigned long long *)counts;
+    if (mem != SKE_MEM_DEVICE) {
+        void *k = stage_buf(c, kStgRowsId, uint64_t(m) * 8, &rc);
+        if (rc) return rc;
+        void *v = stage_buf(c, kStgRowsIdOffs, uint64_t(m) * 8, &rc);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(k, keys, uint64_t(m) * 8, hipMemcpyHostToDevice, c->st));
+        HIPCHK(c, hipMemcpyAsync(v, counts, uint64_t(m) * 8, hipMemcpyHostToDevice, c->st));
+        d_keys = (const unsigned long long *)k;
+        d_counts = (const unsigned long long *)v;
+    }
+    RowsGrpDev *D = (RowsGrpDev *)stage_buf(c, kStgRowsGrp, sizeof(RowsGrpDev), &rc);
+    if (rc) return rc;
+    RowsMrgDev *M = (RowsMrgDev *)stage_buf(c, kStgRowsMrg, sizeof(RowsMrgDev), &rc);
+    if (rc) return rc;
+
+    // the select's sort and its slots: one pass over the caller's keys carries an iota
+    hipError_t e = hipSuccess;
+    unsigned long long *keys_s = (unsigned long long *)scratch_get(c->scratch, kScrKeysSorted, uint64_t(m) * 8, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    uint32_t *idx = (uint32_t *)scratch_get(c->scratch, kScrVals, uint64_t(m) * 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    uint32_t *idx_s = (uint32_t *)scratch_get(c->scratch, kScrValsSorted, uint64_t(m) * 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    RowsMrgWork W{};
+    RowsGrpWork G{};
+    W.counts = d_counts;
+    W.keys_s = keys_s;
+    W.idx_s = idx_s;
+    // the four tile-count arrays side by side (the groups are at most m)
+    const size_t cb = (rows_cnt_bytes(m) + 15) & ~size_t(15);
+    uint8_t *cnts = (uint8_t *)scratch_get(c->scratch, kScrRowsGrpCnt, 4 * cb, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    G.cnt_c = W.cnt_v = (uint32_t *)cnts;
+    G.cnt_e = (uint32_t *)(cnts + cb);
+    G.cnt_l = (uint32_t *)(cnts + 2 * cb);
+    W.cnt_z = (uint32_t *)(cnts + 3 * cb);
+    G.gkey = (unsigned long long *)scratch_get(c->scratch, kScrKeysOrFirst, uint64_t(m) * 8, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    G.lkey = keys_s;  // the sorted keys are read last by the ends, the listed keys written behind them
+    G.gend = (uint32_t *)scratch_get(c->scratch, kScrRowsGrpEnds, uint64_t(m) * 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    G.lcount = (uint32_t *)scratch_get(c->scratch, kScrRowsGrpCounts, uint64_t(m) * 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+    W.zend = (uint32_t *)scratch_get(c->scratch, kScrRowsGrpFlag, uint64_t(m) * 4, &e);
+    if (e != hipSuccess) return scratch_error(c, e);
+
+    HIPCHK(c, launch_rows_iota(idx, m, grid, c->cus, c->st));
+    e = rows_sort_pairs(c->scratch, by == SKE_ROWS_BY_STUDENT, d_keys, keys_s, idx, idx_s, m, c->st);
+    if (e == hipErrorStreamCaptureUnsupported) return scratch_error(c, e);
+    HIPCHK(c, e);
+    HIPCHK(c, launch_rows_grp_init(D, c->st));
+    HIPCHK(c, launch_rows_mrg_ends(W, G, m, M, grid, c->cus, c->st));
+    // the first synchronisation: the groups and the total, before any output is written
+    uint32_t groups = 0;
+    RowsMrgDev hm{};
+    HIPCHK(c, hipMemcpyAsync(&groups, G.cnt_e, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(&hm, M, sizeof hm, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (!rows_merge_total_ok(hm.total, hm.wide)) return SKE_EINVAL;
+
+    HIPCHK(c, launch_rows_grp_counts(G, groups, D, grid, c->cus, c->st));
+    HIPCHK(c, launch_rows_mrg_multi(W, G, groups, M, grid, c->cus, c->st));
+    RowsGrpDev h{};
+    const size_t head = offsetof(RowsGrpDev, hist);  // the accumulators and the select state
+    HIPCHK(c, hipMemcpyAsync(&h, D, head, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(&hm, M, sizeof hm, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    const uint32_t n = uint32_t(h.n);  // <= m
+    if (n == 0) return SKE_OK;
+    HIPCHK(c, launch_rows_grp_median(G, n, D, grid, c->cus, c->st));
+    HIPCHK(c, hipMemcpyAsync(&h, D, head, hipMemcpyDeviceToHost, c->st));
+    const bool fits = n <= cap;
+    uint64_t *d_key = out_key, *d_count = out_count;
+    if (fits) {
+        if (mem != SKE_MEM_DEVICE) {
+            d_key = (uint64_t *)stage_buf(c, kStgRowsLec, uint64_t(n) * 8, &rc);
+            if (rc) return rc;
+            d_count = (uint64_t *)stage_buf(c, kStgRowsEpoch, uint64_t(n) * 8, &rc);
+            if (rc) return rc;
+        }
+        HIPCHK(c, launch_rows_grp_out(G, n, (unsigned long long *)d_key, (unsigned long long *)d_count, grid, c->cus,
+                                      c->st));
+        if (mem != SKE_MEM_DEVICE) {
+            HIPCHK(c, hipMemcpyAsync(out_key, d_key, uint64_t(n) * 8, hipMemcpyDeviceToHost, c->st));
+            HIPCHK(c, hipMemcpyAsync(out_count, d_count, uint64_t(n) * 8, hipMemcpyDeviceToHost, c->st));
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    *n_out = n;
+    *multi_out = hm.multi;
     stats->n = h.n;
     stats->sum = h.sum;
     stats->sumsq = h.sumsq;

@@ -5,6 +5,7 @@
 #include "sketch_common.h"
 #include "sketch_rows_compact.h"
 #include "sketch_rows_group.h"
+#include "sketch_rows_merge.h"
 
 namespace ske {
 
@@ -533,6 +534,35 @@ hipError_t launch_rows_grp_out(const RowsGrpWork &G, uint32_t n, unsigned long l
 // D->bins[tp_bin] += the counted survivors (after launch_rows_last)
 hipError_t launch_rows_profile(const RowsLog &L, const uint32_t *pos, uint32_t m, int valid_filter, uint32_t sod_from,
                                const RowsWork &W, RowsGrpDev *D, unsigned grid, int cus, hipStream_t st);
+// The group merge (DESIGN.md "Exact insights across shards"; the arithmetic is
+// sketch_rows_merge.h's): (key, count) entries in any order to one ascending
+// list of the keys' sums.  The device state beside RowsGrpDev, and the arrays
+// in front of the group-by's back end (launch_rows_grp_counts / _median / _out
+// over G, whose gend is the prefix of the counts here).
+struct RowsMrgDev {
+    unsigned long long total;  // the 64-bit sum of every entry's count
+    unsigned long long multi;  // listed groups with more than one nonzero entry
+    unsigned int wide;         // some count fails rows_merge_entry_ok
+    unsigned int pad;
+};
+struct RowsMrgWork {
+    const unsigned long long *counts;  // n_in entries' counts, as given
+    const unsigned long long *keys_s;  // their keys, sorted,
+    const uint32_t *idx_s;             //   and the entry each sorted position came from
+    uint32_t *cnt_v;  // rows_cnt_bytes(n_in): the counts' u32 tile sums,
+    uint32_t *cnt_z;  //   the nonzero entries' tile counts
+    uint32_t *zend;   // per group: the nonzero entries at or before its end
+};
+// idx[i] = i, i < n
+hipError_t launch_rows_iota(uint32_t *idx, uint32_t n, unsigned grid, int cus, hipStream_t st);
+// M zeroed; then over the sorted positions the tile sums, end counts and nonzero counts, M->total and
+// M->wide, the three scans, and per group its key (G.gkey), the prefix of the counts (G.gend) and of the
+// nonzero flags (W.zend); G.cnt_e[0] = groups
+hipError_t launch_rows_mrg_ends(const RowsMrgWork &W, const RowsGrpWork &G, uint32_t n_in, RowsMrgDev *M,
+                                unsigned grid, int cus, hipStream_t st);
+// M->multi over the groups
+hipError_t launch_rows_mrg_multi(const RowsMrgWork &W, const RowsGrpWork &G, uint32_t groups, RowsMrgDev *M,
+                                 unsigned grid, int cus, hipStream_t st);
 // The compaction (DESIGN.md "Row log compaction"; the arithmetic is
 // sketch_rows_compact.h's), after launch_rows_last over the whole log from the
 // cutoff on (W.flag = survivor per sorted position, `kept` of them among m).
@@ -592,8 +622,8 @@ enum ScratchSlot : int {
     // -- sync
     kScrKeysOrFirst,   // pfadd_exact: sort keys | ske_bf_madd: a link's first-setter table
                        // (up to 4 x bits bytes) | ske_rows_select, ske_rows_group, ske_rows_profile: a
-                       // pass's sort keys, then ske_rows_group's key per group; synchronous calls
-                       // all, never at once
+                       // pass's sort keys, then ske_rows_group's (ske_rows_group_merge's) key per
+                       // group; synchronous calls all, never at once
     kScrKeysSorted,    // pfadd_exact (sketch_order.hip), the row log's reads: sorted keys, then
                        //   ske_rows_group's key per listed group,
     kScrVals,          //   element indices (ske_rows_select: row positions),
@@ -629,9 +659,11 @@ enum ScratchSlot : int {
     kScrRowsSelFlag,   // ske_rows_select, ske_rows_group, ske_rows_profile: a flag byte per row (match, then
                        //   last of its run),
     kScrRowsSelCnt,    //   the totals and the per-tile counts of the flags
-    kScrRowsGrpFlag,   // ske_rows_group: the counted and group-end bits per sorted position,
-    kScrRowsGrpCnt,    //   the three tile-count arrays (counted, group ends, listed groups),
-    kScrRowsGrpEnds,   //   the counted prefix at each group's end,
+    kScrRowsGrpFlag,   // ske_rows_group: the counted and group-end bits per sorted position
+                       //   | ske_rows_group_merge: the nonzero-entry prefix at each group's end (u32),
+    kScrRowsGrpCnt,    //   the three tile-count arrays (counted, group ends, listed groups; the merge: four,
+                       //   the counts' sums, group ends, nonzero entries, listed groups),
+    kScrRowsGrpEnds,   //   the counted prefix (the merge: the prefix of the counts) at each group's end,
     kScrRowsGrpCounts, //   the listed groups' counts (u32), which the median select reads
     kScrRowsKeep,      // ske_rows_compact: a keep byte per log position,
     kScrRowsKeepCnt,   //   the totals and the per-tile counts of the keep bytes
@@ -704,11 +736,13 @@ enum StageSlot : int {
     kStgRowsLec,       // ske_rows_append: the lecture bytes | ske_rows_select / ske_rows_read: the digests on their way out
                        //   | ske_rows_group: the keys on their way to the host,
     kStgRowsLecOffs,   //   ske_rows_append: the lecture offsets,
-    kStgRowsId,        //   the id bytes | ske_rows_select: the ids on their way to the host,
-    kStgRowsIdOffs,    //   the id offsets,
+    kStgRowsId,        //   the id bytes | ske_rows_select: the ids on their way to the host
+                       //   | ske_rows_group_merge: host keys on their way in,
+    kStgRowsIdOffs,    //   the id offsets | ske_rows_group_merge: host counts on their way in,
     kStgRowsEpoch,     //   the epochs (both directions) | ske_rows_group: the counts on their way to the host,
     kStgRowsValid,     //   the valid bytes (both directions)
     kStgRowsGrp,       // ske_rows_group / ske_rows_profile: the statistics, the select state and the bins (RowsGrpDev)
+    kStgRowsMrg,       // ske_rows_group_merge: the total, the wide word and multi (RowsMrgDev)
     kStageSlotCount
 };
 

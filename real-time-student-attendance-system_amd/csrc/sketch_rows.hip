@@ -26,6 +26,9 @@
 // is the last of its run of equal keys).  The sort between the two is
 // rows_sort_pairs (sketch_order.hip), one stable pass per key column.  The
 // group-by and the profile (below, "group-by") start from that same front end.
+// The group merge ("group merge") sums several group-bys' outputs per key: the
+// same sort over the caller's keys, its own flags and prefixes, then the
+// group-by's back end.
 #include "sketch_common.h"
 #include "sketch_internal.h"
 
@@ -474,6 +477,154 @@ __global__ void __launch_bounds__(kRowsBlock) k_rows_profile(const RowsLog L, co
         if (s_b[i]) atomicAdd(&D->bins[i], (unsigned long long)s_b[i]);
 }
 
+// ---- group merge (the arithmetic is sketch_rows_merge.h's)
+//
+// (key, count) entries in any order -- several group-bys' outputs, end to end
+// -- to one ascending list of the keys' sums.  After one rows_sort_pairs of an
+// iota by the keys:
+//   k_rows_mflag   per sorted position the entry's count v, group end, v != 0;
+//                  per tile the u32 sum of v (the wavefront by shuffles, the
+//                  wavefronts through LDS) and the counts of the two flags; per
+//                  workgroup one 64-bit add of the true total and an OR of
+//                  "some v >= 2^32", which the host reads before any output
+//   k_rows_scan    three times: the tile sums and counts to their prefixes
+//   k_rows_mends   per group end, at its group rank: the key, the inclusive
+//                  prefix of v (tile prefix + the earlier wavefronts' totals +
+//                  a wave64 inclusive scan) and of the nonzero flags
+//   k_rows_mmulti  per group: listed with more than one nonzero entry?
+// and the group-by's back end over the prefix of v (k_rows_gcount, k_rows_scan,
+// k_rows_gplace, the select rounds, k_rows_gout).  No thread waits for another
+// workgroup; every accumulation is an integer's, so the answer does not depend
+// on the order of the entries or of the workgroups.
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_iota(uint32_t *idx, uint32_t n) {
+    const uint64_t stride = uint64_t(gridDim.x) * kRowsBlock;
+    for (uint64_t i = uint64_t(blockIdx.x) * kRowsBlock + threadIdx.x; i < n; i += stride) idx[i] = uint32_t(i);
+}
+
+__global__ void k_rows_minit(RowsMrgDev *M) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) M->total = 0, M->multi = 0, M->wide = 0, M->pad = 0;
+}
+
+// the inclusive prefix of v over the tile's threads (every thread of the
+// workgroup calls it); *all = the tile's sum.  u32 arithmetic: the caller
+// bounds the total.
+__device__ __forceinline__ uint32_t rows_tile_prefix(uint32_t v, unsigned int *s_w, uint32_t *all) {
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d, 64);
+        if (lane >= uint32_t(d)) x += y;
+    }
+    if (lane == 63) s_w[w] = x;
+    __syncthreads();
+    uint32_t before = 0, sum = 0;
+#pragma unroll
+    for (int k = 0; k < kRowsWaves; k++) {
+        const uint32_t s = s_w[k];
+        if (uint32_t(k) < w) before += s;
+        sum += s;
+    }
+    __syncthreads();  // the LDS words are written again in the next turn
+    *all = sum;
+    return before + x;
+}
+
+// what sorted position j < n holds: the entry's count and whether it ends its key's run
+__device__ __forceinline__ unsigned long long rows_mrg_entry(const RowsMrgWork &W, uint64_t j, uint32_t n,
+                                                             bool *gend) {
+    *gend = j + 1 == n || W.keys_s[j] != W.keys_s[j + 1];
+    return W.counts[W.idx_s[j]];
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_mflag(const RowsMrgWork W, const RowsGrpWork G, uint32_t n,
+                                                            RowsMrgDev *M) {
+    __shared__ unsigned int s_ok[kRowsWaves], s_ref[kRowsWaves];
+    __shared__ unsigned long long s_tot[kRowsWaves];
+    __shared__ unsigned int s_wide;
+    if (threadIdx.x == 0) s_wide = 0;
+    __syncthreads();
+    const uint64_t tiles = rows_tiles(n);
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned long long tot = 0;
+    bool wide = false;
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t j = t * kRowsBlock + threadIdx.x;
+        unsigned long long v = 0;
+        bool gend = false;
+        if (j < n) {
+            v = rows_mrg_entry(W, j, n, &gend);
+            if (rows_merge_entry_ok(v)) tot += v;
+            else wide = true;
+        }
+        // the tile's u32 sum: the wavefront by shuffles, the wavefronts through LDS
+        uint32_t x = uint32_t(v);
+        for (int o = 32; o; o >>= 1) x += __shfl_xor(x, o, 64);
+        if (lane == 0) s_ok[w] = x;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t a = 0;
+#pragma unroll
+            for (int k = 0; k < kRowsWaves; k++) a += s_ok[k];
+            G.cnt_c[4 + t] = a;
+            G.cnt_c[4 + tiles + t] = 0;
+        }
+        __syncthreads();
+        rows_tile_count(gend, false, G.cnt_e, tiles, t, s_ok, s_ref);
+        rows_tile_count(v != 0, false, W.cnt_z, tiles, t, s_ok, s_ref);
+    }
+    tot = wave_sum64(tot);
+    const unsigned long long any_wide = __ballot(wide);
+    if (lane == 0) {
+        s_tot[w] = tot;
+        if (any_wide) atomicOr(&s_wide, 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < kRowsWaves; k++) tot += s_tot[k];
+        if (tot) atomicAdd(&M->total, tot);
+        if (s_wide) atomicOr(&M->wide, 1u);
+    }
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_mends(const RowsMrgWork W, const RowsGrpWork G, uint32_t n) {
+    __shared__ unsigned int s_ok[kRowsWaves];
+    const uint64_t tiles = rows_tiles(n);
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t j = t * kRowsBlock + threadIdx.x;
+        unsigned long long v = 0;
+        bool gend = false;
+        if (j < n) v = rows_mrg_entry(W, j, n, &gend);
+        const bool nz = v != 0;
+        uint32_t all;
+        const uint32_t pv = rows_tile_prefix(uint32_t(v), s_ok, &all);
+        const uint32_t rz = rows_tile_rank(nz, s_ok);
+        const uint32_t re = rows_tile_rank(gend, s_ok);
+        if (!gend) continue;
+        const uint64_t g = uint64_t(G.cnt_e[4 + t]) + re;
+        G.gkey[g] = W.keys_s[j];
+        G.gend[g] = G.cnt_c[4 + t] + pv;
+        W.zend[g] = W.cnt_z[4 + t] + rz + (nz ? 1u : 0u);
+    }
+}
+
+__global__ void __launch_bounds__(kRowsBlock) k_rows_mmulti(const RowsMrgWork W, const RowsGrpWork G, uint32_t groups,
+                                                             RowsMrgDev *M) {
+    __shared__ unsigned long long s_m[kRowsWaves];
+    unsigned long long m = 0;
+    const uint64_t stride = uint64_t(gridDim.x) * kRowsBlock;
+    for (uint64_t g = uint64_t(blockIdx.x) * kRowsBlock + threadIdx.x; g < groups; g += stride)
+        if (rows_merge_multi(rows_merge_sum(G.gend, g), rows_merge_entries(W.zend, g))) m += 1;
+    m = wave_sum64(m);
+    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < kRowsWaves; k++) m += s_m[k];
+        if (m) atomicAdd(&M->multi, m);
+    }
+}
+
 // ---- compaction (the arithmetic is sketch_rows_compact.h's)
 //
 // After the front end over the whole log (every lecture, epoch >= keep_since,
@@ -709,6 +860,38 @@ hipError_t launch_rows_grp_out(const RowsGrpWork &G, uint32_t n, unsigned long l
                                unsigned long long *out_count, unsigned grid, int cus, hipStream_t st) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_rows_gout, dim3(grid_of(n, grid, cus)), dim3(kRowsBlock), 0, st, G, n, out_key, out_count);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_iota(uint32_t *idx, uint32_t n, unsigned grid, int cus, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rows_iota, dim3(grid_of(n, grid, cus)), dim3(kRowsBlock), 0, st, idx, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_mrg_ends(const RowsMrgWork &W, const RowsGrpWork &G, uint32_t n_in, RowsMrgDev *M,
+                                unsigned grid, int cus, hipStream_t st) {
+    hipLaunchKernelGGL(k_rows_minit, dim3(1), dim3(64), 0, st, M);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || n_in == 0) return e;
+    const unsigned g = grid_of(n_in, grid, cus);
+    hipLaunchKernelGGL(k_rows_mflag, dim3(g), dim3(kRowsBlock), 0, st, W, G, n_in, M);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = rows_scan(G.cnt_c, n_in, st);
+    if (e != hipSuccess) return e;
+    e = rows_scan(G.cnt_e, n_in, st);
+    if (e != hipSuccess) return e;
+    e = rows_scan(W.cnt_z, n_in, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rows_mends, dim3(g), dim3(kRowsBlock), 0, st, W, G, n_in);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_mrg_multi(const RowsMrgWork &W, const RowsGrpWork &G, uint32_t groups, RowsMrgDev *M,
+                                 unsigned grid, int cus, hipStream_t st) {
+    if (groups == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rows_mmulti, dim3(grid_of(groups, grid, cus)), dim3(kRowsBlock), 0, st, W, G, groups, M);
     return hipGetLastError();
 }
 

@@ -1121,6 +1121,8 @@ class LibsketchCountsOps:
         self.sets = [t[0] for t in c._tracks] + ([c._late_track[0]] if c._late_track is not None else [])
         self.profile = c._profile
         self.tally = c._lectures
+        self.keeps_records = bool(c.keeps_records)
+        self.late_from = c.late_from
         self.view = None
 
     # -- what must agree across the ranks, and the view
@@ -1144,7 +1146,8 @@ class LibsketchCountsOps:
         hh_log2 = max([cl.hh_info(s)["capacity"].bit_length() - 1 for s in self.sets], default=0)
         tally_log2 = cl.tally_info(self.tally)["capacity"].bit_length() - 1 if self.tally is not None else 0
         return [len(self.cms_keys)] + dims + [c.late_from] + tracks + [
-            int(self.profile is not None), int(c._day_insight), int(self.tally is not None), hh_log2, tally_log2]
+            int(self.profile is not None), int(c._day_insight), int(self.tally is not None), int(c.keeps_records),
+            hh_log2, tally_log2]
 
     def make_view(self, suffix, world: int, capacity_log2=None, lecture_capacity_log2=None):
         """The merged view: a second ``StudentCounts`` on the same client whose
@@ -1262,6 +1265,60 @@ class LibsketchCountsOps:
                                     None if none else events, None if none else valid, n, dropped_events,
                                     dropped_valid, overflow)
 
+    # -- the row log's group-bys
+    def _u64_outputs(self, n: int):
+        """Two device arrays of ``n`` u64 words for a library call to fill, as
+        ``engine._two_calls``' ``alloc`` returns them.  Not filled (only what
+        the call writes is read), and torch is waited for: the allocation's
+        own work on torch's stream is over before the context's stream writes."""
+        k, v = (self.torch.empty(max(int(n), 2) * 8, dtype=self.torch.uint8, device=self.device) for _ in range(2))
+        self._sync_torch()
+        return (k, v), (k.data_ptr(), v.data_ptr())
+
+    def rows_group_export(self, which: str):
+        """The local log's group-by, its outputs on the device: ``(keys, counts,
+        n, rows, complete)`` -- 8 n bytes each as uint8 tensors, and the words.
+        ``which`` "attended", "late" or "invalid": by student with
+        ``StudentCounts._EXACT``'s filter; "lectures": by lecture, every row."""
+        from . import _lib
+        from .engine import rows_group_dev
+        c, cl = self.counts, self.client
+        # the window and the filter words as rows_group makes them, from exact_counts' own options
+        opt = {} if which == "lectures" else c._EXACT[which]
+        by = _lib.SKE_ROWS_BY_LECTURE if which == "lectures" else _lib.SKE_ROWS_BY_STUDENT
+        lec, lo, hi, vf, sod = cl._rows_window(None, None, None, opt.get("valid"),
+                                               c.late_from if opt.get("late") else None)
+        self._sync_torch()
+        made, n, stats, complete = rows_group_dev(cl.ctx, cl.rows_rid(c._records), by, lec, lo, hi, vf, sod,
+                                                  self._u64_outputs)
+        k, v = made if made is not None else self._u64_outputs(0)[0]
+        return k[:8 * n], v[:8 * n], n, stats["rows"], int(complete)
+
+    def rows_profile_read(self) -> np.ndarray:
+        """The local log's rows per weekday and hour: 168 uint64."""
+        return self.client.rows_profile(self.counts._records).reshape(-1)
+
+    def rows_group_merge(self, by: str, keys_u8, counts_u8, n_in: int, groups: bool = True):
+        """One ``ske_rows_group_merge`` over ``n_in`` gathered entries (8 n_in
+        bytes each, device uint8 tensors): ``(keys, counts, stats, multi)``, the
+        listed groups as host uint64 arrays."""
+        from . import _lib
+        from .engine import rows_group_merge
+        keys_u8, counts_u8 = keys_u8.contiguous(), counts_u8.contiguous()
+        self._sync_torch()
+        k, v, stats, multi = rows_group_merge(
+            self.client.ctx, _lib.SKE_ROWS_BY_STUDENT if by == "student" else _lib.SKE_ROWS_BY_LECTURE,
+            keys_u8.data_ptr(), counts_u8.data_ptr(), n_in, _lib.SKE_MEM_DEVICE, groups, self._u64_outputs)
+        n = stats["n"] if k is not None else 0
+        host = [np.zeros(0, np.uint64) if k is None else t[:8 * n].cpu().numpy().view(np.uint64).copy()
+                for t in (k, v)]
+        return host[0], host[1], stats, multi
+
+    def view_lecture_names(self) -> list:
+        """The lecture names of the view's tally listing, as of the last ``merge()``."""
+        names, *_ = self.client.tally_list(self.view._lectures)
+        return list(names)
+
 
 class ShardedCounts:
     """A ``StudentCounts`` whose swipes are spread over ``world`` ranks: the
@@ -1279,7 +1336,10 @@ class ShardedCounts:
     every swipe would hold, bit for bit.
 
     Counting methods (``update``, ``count_packed``, ``update_messages*``,
-    ``timed``, ``counts_lectures``) go to the local object; the queries
+    ``timed``, ``counts_lectures``) and the row log's own calls (``records``,
+    ``records_info``, ``compact_records``: this rank's rows, which under
+    sharding by lecture are all the rows of the lectures it owns) go to the
+    local object; the queries
     (``attended``, ``invalid``, ``late``, ``top_*``, ``population``,
     ``reference_threshold``, ``lecture_events``, ``lecture_rankings``,
     ``by_day``, ``by_hour_of_week``) answer from the merged view as of the last
@@ -1302,11 +1362,20 @@ class ShardedCounts:
     not fit leaves ``complete`` False.  The ranks' table dimensions,
     ``late_from`` and options must agree, else ``ValueError`` on every rank.
 
+    With ``records=`` on every rank's counts, ``exact_counts``,
+    ``exact_by_day``, ``exact_lecture_rankings`` and ``exact_insights`` (all
+    COLLECTIVE) give ``StudentCounts``' exact answers over every rank's rows
+    (DESIGN.md §22): sharding by lecture puts each (lecture, timestamp,
+    student) on one rank, so each group-by is the per-key sum of the ranks'
+    group-bys -- the groups travel, never the rows -- and ``split_lectures``
+    says whether that precondition held.  ``ValueError`` without records.
+
     The device operations sit behind ``ops`` (``LibsketchCountsOps``) and the
     collectives behind ``transport`` (``Collectives``), so the gather, padding
     and ordering logic runs under gloo on CPU tensors in the tests."""
 
-    _LOCAL = ("update", "count_packed", "update_messages", "update_messages_packed")
+    _LOCAL = ("update", "count_packed", "update_messages", "update_messages_packed", "records", "records_info",
+              "compact_records")
     _VIEW = ("attended", "invalid", "late", "top_attended", "top_invalid", "top_late", "population",
              "reference_threshold", "lecture_events", "lecture_rankings", "by_day", "by_hour_of_week")
 
@@ -1395,6 +1464,120 @@ class ShardedCounts:
         """COLLECTIVE: ``merge()``, then the merged view's ``insights(**kw)``."""
         self.merge()
         return self.view.insights(**kw)
+
+    # -- the exact insights: the ranks' row-log group-bys merged (DESIGN.md section 22)
+
+    @property
+    def keeps_records(self) -> bool:
+        """Whether the local counts keep a row log (the ranks agree: the
+        constructor compared it)."""
+        return bool(getattr(self.ops, "keeps_records", False))
+
+    @property
+    def _lectures(self):
+        """The local tally's name (``AttendanceProcessor.fetch_attendance_data``
+        joins this rank's rows to its own lectures' names)."""
+        return self.local._lectures
+
+    def _need_records(self) -> None:
+        if not self.keeps_records:
+            raise ValueError("no records")
+
+    def _merged_groups(self, which: str, groups: bool = True):
+        """One rank-local group-by, one ``gather_ints``, one ``all_gather``, one
+        merge: ``(rows_group's dict with "rows" summed and "complete" the AND
+        of the ranks', multi)``."""
+        import torch
+        ops, tr, world = self.ops, self.transport, self.world
+        by = "lecture" if which == "lectures" else "student"
+        keys, counts, n, rows, complete = ops.rows_group_export(which)
+        meta = tr.gather_ints([n, rows, complete], ops.device)
+        # padded to the largest rank, a multiple of 4 entries; a pad is (key 0, count 0) and vanishes
+        nmax = (int(meta[:, 0].max()) + 3) & ~3
+        if nmax:
+            got = tr.all_gather(torch.cat([self._pad(keys, 8 * nmax), self._pad(counts, 8 * nmax)]))
+            # [world, keys | counts] to every rank's keys, then every rank's counts: two flat arrays
+            flat = got.view(world, 2, 8 * nmax).transpose(0, 1).contiguous()
+            k, c, stats, multi = ops.rows_group_merge(by, flat[0].reshape(-1), flat[1].reshape(-1), world * nmax,
+                                                      groups)
+        else:
+            from .client_rows import group_stats
+            k, c, multi = np.zeros(0, np.uint64), np.zeros(0, np.uint64), 0
+            stats = group_stats([])
+        stats = dict(stats, rows=int(meta[:, 1].sum()))
+        stats["median"] = (stats["med_lo"] + stats["med_hi"]) / 2
+        k = np.asarray(k, np.uint64)
+        return {"keys": k.view(np.int64) if by == "student" else k, "counts": np.asarray(c, np.uint64),
+                "stats": stats, "complete": bool(meta[:, 2].all())}, int(multi)
+
+    def _split_lectures(self) -> int:
+        return self._merged_groups("lectures", groups=False)[1]
+
+    def exact_counts(self, which: str, groups: bool = True) -> dict:
+        """COLLECTIVE.  ``StudentCounts.exact_counts`` over every rank's rows:
+        each rank's ``rows_group`` by student stays on its device, one
+        all-gather carries the (id, count) pairs -- never a swipe -- and one
+        ``ske_rows_group_merge`` sums them per student.  ``rows_group``'s dict,
+        ``stats["rows"]`` the ranks' sum, ``complete`` true when every rank's
+        log is, plus ``"split_lectures"``: the lectures (by digest) that more
+        than one rank holds rows of, from a second, by-lecture merge.  ``0``:
+        every lecture's rows lay on one rank -- the swipes were sharded by
+        lecture -- and the answer is the one-context answer, bit for bit.
+        Nonzero: a lecture was split; the sums are still right unless the same
+        (lecture, timestamp, student) row reached two ranks, which then counts
+        once per rank (the upsert collapse is rank-local).  Nothing is raised."""
+        return self._exact_counts(which, groups, None)
+
+    def _exact_counts(self, which: str, groups: bool, split) -> dict:
+        """``exact_counts``; ``split``: the by-lecture merge's ``multi`` when the
+        caller has it already (None: one more merge finds it)."""
+        self._need_records()
+        if which not in ("attended", "late", "invalid"):
+            raise ValueError('which is "attended", "invalid" or "late"')
+        out, _ = self._merged_groups(which, groups)
+        out["split_lectures"] = self._split_lectures() if split is None else split
+        return out
+
+    def exact_by_day(self) -> dict:
+        """COLLECTIVE.  ``StudentCounts.exact_by_day`` over every rank's rows:
+        the sum of the ranks' 168 weekday-by-hour bins."""
+        from .analysis import exact_by_day_format
+        self._need_records()
+        mine = np.ascontiguousarray(self.ops.rows_profile_read(), dtype=np.uint64).view(np.int64)
+        return exact_by_day_format(self.transport.sum_ints(mine, self.ops.device).view(np.uint64))
+
+    def exact_lecture_rankings(self, k: int = 3) -> dict:
+        """COLLECTIVE.  ``StudentCounts.exact_lecture_rankings`` over every
+        rank's rows: the by-lecture merge, the names from the merged view's
+        tally listing as of the last ``merge()``; carries ``"complete"`` and
+        ``"split_lectures"`` (see ``exact_counts``)."""
+        from .analysis import exact_rankings_format
+        self._need_records()
+        if self.ops.tally is None:
+            raise ValueError("exact_lecture_rankings needs lecture_counts (the lecture names)")
+        g, multi = self._merged_groups("lectures")
+        return dict(exact_rankings_format(g, self.ops.view_lecture_names(), k), split_lectures=multi)
+
+    def exact_insights(self, lecture_k: int | None = 3) -> list:
+        """COLLECTIVE.  ``merge()`` (for the lecture names), then
+        ``StudentCounts.exact_insights`` over every rank's rows: the same five
+        entries from the merged group-bys, each with ``complete`` and
+        ``split_lectures``."""
+        from .analysis import exact_insight_entries
+        self._need_records()
+        if lecture_k is not None and self.ops.tally is None:
+            raise ValueError("exact_lecture_rankings needs lecture_counts (the lecture names)")
+        self.merge()
+        if lecture_k is not None:
+            ranks = self.exact_lecture_rankings(lecture_k)
+            split = ranks["split_lectures"]
+        else:
+            ranks, split = None, self._split_lectures()
+        late = self._exact_counts("late", True, split)
+        by_day = self.exact_by_day()
+        att = self._exact_counts("attended", True, split)
+        inv = self._exact_counts("invalid", True, split)
+        return exact_insight_entries(late, by_day, ranks, att, inv, self.ops.late_from)
 
 
 def _delegate(target: str, name: str):

@@ -340,6 +340,96 @@ def rows_group(ctx: Context, rid: int, by: int, lecture: bytes | None, since: in
     return keys[:n], counts[:n], stats, bool(complete.value)
 
 
+def _two_calls(call, n_out, want_groups: bool, alloc):
+    """``cap = 0`` first (the statistics, and how many groups there are), then
+    ``alloc(n)`` -- ``(what to return, the two pointers)`` -- and the call
+    that fills them; returns what ``alloc`` made, or None when nothing is
+    listed or ``want_groups`` is false."""
+    def once(ptrs, cap) -> bool:
+        try:
+            call(ptrs, cap)
+        except SketchLibError as e:
+            if e.code != SKE_EROWSSPACE:
+                raise
+            return False
+        return int(n_out.value) <= cap
+
+    if once((None, None), 0) or not want_groups:
+        return None
+    cap = int(n_out.value)
+    made, ptrs = alloc(cap)
+    if not once(tuple(C.c_void_p(int(p)) for p in ptrs), cap):
+        raise SketchLibError(SKE_EROWSSPACE, "ERR row log selection does not fit the output")
+    return made
+
+
+def _host_groups(cap: int):
+    keys, counts = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+    return (keys, counts), (keys.ctypes.data, counts.ctypes.data)
+
+
+def rows_group_dev(ctx: Context, rid: int, by: int, lecture: bytes | None, since: int, until: int, valid_filter: int,
+                   sod_from: int, alloc, want_groups: bool = True):
+    """ske_rows_group with ``SKE_MEM_DEVICE`` outputs: ``(made, n, stats,
+    complete)``.  The statistics are asked for first (``cap = 0``); with ``n``
+    groups listed, ``alloc(n)`` returns ``(made, (keys pointer, counts
+    pointer))`` -- device arrays of ``n`` u64 words each, the caller's (torch
+    tensors, say) -- which a second call fills; ``made`` is handed back (None
+    when nothing is listed or ``want_groups`` is false)."""
+    n_out, complete, st = C.c_uint64(), C.c_int(), RowsGroupStats()
+    lec = None if lecture is None else C.c_char_p(lecture)
+    llen = 0 if lecture is None else len(lecture)
+    head = (int(rid), int(by), lec, llen, int(since), int(until), int(valid_filter), int(sod_from))
+
+    def call(ptrs, cap):
+        ctx.call("ske_rows_group", *head, *ptrs, cap, C.byref(n_out), C.byref(st), C.byref(complete), SKE_MEM_DEVICE)
+
+    made = _two_calls(call, n_out, want_groups, alloc)
+    stats = {k: int(getattr(st, k)) for k, _ in RowsGroupStats._fields_}
+    return made, int(n_out.value), stats, bool(complete.value)
+
+
+def rows_group_merge(ctx: Context, by: int, keys, counts, n_in: int, mem: int = SKE_MEM_HOST,
+                     want_groups: bool = True, alloc=None):
+    """ske_rows_group_merge: ``(keys, counts, stats, multi)`` -- the ``n_in``
+    (key, count) entries summed per key, the keys with a nonzero sum ascending
+    (signed by student, unsigned by lecture).  ``SKE_MEM_HOST``: ``keys`` and
+    ``counts`` are contiguous numpy arrays of 8-byte words and the answer comes
+    as uint64 arrays.  ``SKE_MEM_DEVICE``: they are device pointers, and
+    ``alloc(n)`` returns ``((keys, counts), (keys pointer, counts pointer))``
+    for the ``n`` listed groups, as for ``rows_group_dev``; the pair it made is
+    returned (``(None, None)`` when nothing is listed).  Two calls: ``cap = 0``
+    first, then the fill; ``want_groups`` False stops after the first.
+    ``stats`` holds ske_rows_group_stats_t's fields as Python ints, ``rows`` 0."""
+    n_in = int(n_in)
+    if n_in < 0:
+        raise ValueError("n_in is a count")
+    if mem == SKE_MEM_HOST:
+        if n_in:
+            for a in (keys, counts):
+                if not (isinstance(a, np.ndarray) and a.dtype.itemsize == 8 and a.flags.c_contiguous
+                        and a.size >= n_in):
+                    raise ValueError("keys and counts are contiguous numpy arrays of n_in 8-byte words")
+        kp = C.c_void_p(keys.ctypes.data) if n_in else None
+        cp = C.c_void_p(counts.ctypes.data) if n_in else None
+        alloc = _host_groups
+    else:
+        if alloc is None and want_groups:
+            raise ValueError("device outputs need alloc")
+        kp, cp = (C.c_void_p(int(keys)), C.c_void_p(int(counts))) if n_in else (None, None)
+    n_out, multi, st = C.c_uint64(), C.c_uint64(), RowsGroupStats()
+
+    def call(ptrs, cap):
+        ctx.call("ske_rows_group_merge", int(by), kp, cp, n_in, *ptrs, cap, C.byref(n_out), C.byref(st),
+                 C.byref(multi), int(mem))
+
+    made = _two_calls(call, n_out, want_groups, alloc)
+    stats = {k: int(getattr(st, k)) for k, _ in RowsGroupStats._fields_}
+    if made is None:
+        made = (np.zeros(0, np.uint64), np.zeros(0, np.uint64)) if mem == SKE_MEM_HOST else (None, None)
+    return made[0], made[1], stats, int(multi.value)
+
+
 def rows_profile(ctx: Context, rid: int, lecture: bytes | None, since: int, until: int, valid_filter: int,
                  sod_from: int):
     """ske_rows_profile: ``(bins, rows, complete)`` -- the counted rows per
